@@ -5,15 +5,22 @@ EntropyBottleneck + 12-slice GaussianConditional likelihoods, ViT decoder, unpat
 of 64 synthetic 256x256 RGB images with K=144 kept patches, bf16 MFMA operands (f32 accumulate,
 f32 entropy models).  The forward is replayed as a HIP graph; inputs are resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
     python bench.py --enc-dim 1024 --enc-depth 24 --enc-heads 16 --batch 128     # BASELINE config 4
+
+A plain run sets up, warms up, times the K steps and prints the result line (``value`` images/s and
+``ms_per_step`` over exactly K timed steps).  ``--dump-outputs DIR`` then writes what the last timed step
+returned (x_hat, the y / z likelihoods) as DIR/<name>.npy in float32; inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.  Everything else -- the roofline
+below, the K=64 / MAE / forward_loss / training lines, the CPU baseline -- runs only with ``--full`` (each
+part still has its ``--no-...`` switch there).
 
 Multi-GPU: images are independent, so every rank runs its own batch with no
 collective on the data path ("weak" scaling); the barrier + max-over-ranks timing follows the
 driver contract.  Rank 0 prints one JSON line.
 
-Roofline (rank 0): one extra eager forward records every library launch with its kernel family and
+Roofline (rank 0, ``--full``): one extra eager forward records every library launch with its kernel family and
 algorithmic FLOPs; each family's launches are then replayed back to back between a HIP event pair on
 the stream they run on, giving the family's kernel time per forward (DESIGN.md §5 lists the shape ->
 family mapping; tools/family_summary.py gives the same split from a rocprofv3 kernel trace):
@@ -54,18 +61,22 @@ def parse():
     ap.add_argument("--enc-heads", type=int, default=12)
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline, the K=64 / MAE / forward_loss / training lines and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="all-threads oracle sample length")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)  # internal: one CPU-baseline leg
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--dump-launches", default=None, help="write every launch of one forward with its family and shape")
+    ap.add_argument("--dump-launches", default=None, help="with --full: write every launch of one forward with its family and shape")
     ap.add_argument("--train-steps", type=int, default=10, help="training steps timed after the inference run")
     ap.add_argument("--train-warmup", type=int, default=3)
     ap.add_argument("--train-batch", type=int, default=64)
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--mae-large", action="store_true",
-                    help="add the literal BASELINE config 4 line (MAE ViT-L dec512d8b, batch 128, bf16)")
+                    help="with --full: add the literal BASELINE config 4 line (MAE ViT-L dec512d8b, batch 128, bf16)")
     ap.add_argument("--no-dp-rehearsal", dest="dp_rehearsal", action="store_false",
                     help="skip the one-rank RCCL GradSync overlap measurement at N=1")
     ap.add_argument("--no-distortion", dest="distortion_line", action="store_false",
@@ -730,8 +741,9 @@ def progress(msg):
 def time_forward(model, imgs, scores, steps, warmup, use_graph, world, dev, backend, barrier):
     """the timed region: `warmup` untimed forwards, then exactly `steps` forwards (replays of one HIP graph)
     between barrier + synchronize on both sides; returns (max-over-ranks wall seconds, median step ms from
-    per-step HIP events recorded on the stream -- no host sync inside the region)"""
+    per-step HIP events recorded on the stream -- no host sync inside the region, the last timed step's output)"""
     graph = None
+    last = [None]
     with torch.no_grad():
         if use_graph:
             s = torch.cuda.Stream()
@@ -742,13 +754,13 @@ def time_forward(model, imgs, scores, steps, warmup, use_graph, world, dev, back
             torch.cuda.current_stream().wait_stream(s)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                model(imgs, scores)
+                last[0] = model(imgs, scores)  # the graph's output buffers: every replay writes them
 
             def step():
                 graph.replay()
         else:
             def step():
-                model(imgs, scores)
+                last[0] = model(imgs, scores)
 
         for _ in range(warmup):
             step()
@@ -766,7 +778,29 @@ def time_forward(model, imgs, scores, steps, warmup, use_graph, world, dev, back
     ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(steps))
     med = ms[len(ms) // 2] if len(ms) % 2 else 0.5 * (ms[len(ms) // 2 - 1] + ms[len(ms) // 2])
     del graph
-    return el, med
+    return el, med, last[0]
+
+
+DUMP_LIMIT = 48 << 20  # bytes over all dumped arrays
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: what a caller of the timed forward receives (x_hat, likelihoods y / z) as
+    <path>/<name>.npy in float32.  Above DUMP_LIMIT bytes in all, every array is cut to its proportional
+    share: a sorted sample of its flattened elements at indices drawn from a fixed seed (the same indices
+    for the same shapes, so two runs stay comparable element for element)."""
+    import numpy as np
+
+    arrs = {"x_hat": out["x_hat"], "likelihoods_y": out["likelihoods"]["y"], "likelihoods_z": out["likelihoods"]["z"]}
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    for i, (name, a) in enumerate(arrs.items()):
+        if total > DUMP_LIMIT:
+            keep = max(1, int(a.size * DUMP_LIMIT / total))
+            idx = np.sort(np.random.default_rng(1234 + i).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def k64_line(args, dev, world, rank, barrier, dtype):
@@ -780,8 +814,8 @@ def k64_line(args, dev, world, rank, barrier, dtype):
     m.distortion = "none"
     L = m.encoder_embed.num_patches
     imgs, scores = synthetic_inputs(args.batch, args.img, L, 1000 + rank, dev)
-    el, med = time_forward(m, imgs, scores, args.steps, args.warmup, not args.no_graph, world, dev, args.backend,
-                           barrier)
+    el, med, _ = time_forward(m, imgs, scores, args.steps, args.warmup, not args.no_graph, world, dev, args.backend,
+                              barrier)
     gf = sum(gflop_per_image(m).values())
     v = world * args.batch * args.steps / el
     del m
@@ -1019,36 +1053,42 @@ def main():
     gf_img = sum(gf.values())
 
     progress(f"forward: batch {args.batch}, {args.steps} timed steps")
-    el, med_ms = time_forward(model, imgs, scores, args.steps, args.warmup, not args.no_graph, world, dev, args.backend,
-                              barrier)
+    el, med_ms, out = time_forward(model, imgs, scores, args.steps, args.warmup, not args.no_graph, world, dev,
+                                   args.backend, barrier)
+    if args.dump_outputs and rank == 0:
+        progress(f"writing the last step's outputs to {args.dump_outputs}")
+        dump_outputs(out, args.dump_outputs)
+    del out
+
+    # everything below the headline figure (roofline, side lines, training, CPU baseline) runs under --full only
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         progress("roofline: per-family replays")
         roof = roofline_report(model, imgs, scores, args.batch, dump=args.dump_launches,
                                profiled=vitb_default(args) and args.batch == 64 and args.img == 256)
 
     k64 = None
-    if args.k64_line and vitb_default(args):
+    if args.full and args.k64_line and vitb_default(args):
         progress("config 2' (K=64) line")
         k64 = k64_line(args, dev, world, rank, barrier, dtype)
 
     mae_l = None
-    if args.mae_large:
+    if args.full and args.mae_large:
         progress("config 4 (MAE ViT-L, batch 128) line")
         mae_l = mae_large_line(args, dev, world, rank, barrier, dtype)
 
     mae_t = None
-    if args.mae_train_line and vitb_default(args) and world == 1:
+    if args.full and args.mae_train_line and vitb_default(args) and world == 1:
         progress("MAE ViT-B training line")
         mae_t = mae_train_line(args, dev, world, rank, barrier, dtype)
 
     dist_line = None
-    if args.distortion_line and vitb_default(args):
+    if args.full and args.distortion_line and vitb_default(args):
         progress("forward_loss line")
         dist_line = distortion_line(model, imgs, scores, args, world, dev, barrier)
 
     train = None
-    if not args.no_train and args.train_steps > 0:
+    if args.full and not args.no_train and args.train_steps > 0:
         progress("training step")
         train = train_bench(model, args, rank, world, dev, barrier)
 
@@ -1083,7 +1123,7 @@ def main():
     if train is not None:
         rec["train"] = train
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             progress("cpu baseline")
             rec["cpu_baseline"] = cpu_baseline(args, kw)
         print(json.dumps(rec), flush=True)

@@ -311,7 +311,7 @@ def test_bench_two_ranks_gloo_prints_one_line():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
            "--steps", "2", "--warmup", "1", "--batch", "4", "--train-steps", "1", "--train-warmup", "1",
-           "--train-batch", "2", "--kernel-reps", "2"]
+           "--train-batch", "2", "--kernel-reps", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -485,7 +485,7 @@ def test_bench_spawns_ranks_without_launcher():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
            "--warmup", "1", "--batch", "4", "--train-steps", "1", "--train-warmup", "1", "--train-batch", "2",
-           "--no-roofline"]
+           "--no-roofline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -82,3 +82,51 @@ def test_bench_rejects_gpus_world_size_mismatch():
                        env=env, timeout=120)
     assert r.returncode == 2 and "WORLD_SIZE=1" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_outputs_float32_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: x_hat and the y / z likelihoods as float32 .npy; above the byte limit every array
+    is a proportional sample at the same seeded indices from run to run"""
+    import numpy as np
+    import torch
+
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    out = {"x_hat": torch.rand(3, 3, 16, 16, generator=g).bfloat16(), "loss": (torch.zeros(()),) * 3,
+           "likelihoods": {"y": torch.rand(3, 20, 4, 4, generator=g), "z": torch.rand(3, 7, 1, 1, generator=g)}}
+    full = {"x_hat": out["x_hat"].float().numpy(), "likelihoods_y": out["likelihoods"]["y"].numpy(),
+            "likelihoods_z": out["likelihoods"]["z"].numpy()}
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    for k, v in full.items():
+        a = np.load(tmp_path / "a" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, v)
+    total = sum(v.nbytes for v in full.values())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", total // 3)
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    bench.dump_outputs(out, str(tmp_path / "c"))
+    got = 0
+    for k, v in full.items():
+        b, c = np.load(tmp_path / "b" / (k + ".npy")), np.load(tmp_path / "c" / (k + ".npy"))
+        assert b.dtype == np.float32 and b.ndim == 1 and 0 < b.size < v.size
+        assert np.array_equal(b, c) and np.isin(b, v).all()
+        got += b.nbytes
+    assert got <= total // 3
+
+
+def test_bench_full_is_off_by_default():
+    """bench.py's command line: --full and --dump-outputs are off unless given, --steps is taken as given"""
+    import sys
+
+    import bench
+
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+        a = bench.parse()
+        assert a.full is False and a.steps == 3 and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "d"
+    finally:
+        sys.argv = argv

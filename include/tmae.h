@@ -526,6 +526,9 @@ int tmae_eb_aux_bwd(const tmae_eb_params* params, const float* target, const flo
 int tmae_bpp_bwd(const float* lik, const float* gout, float* dlik, long long n, double num_pixels, void* stream);
 /* patchify of the reconstruction gradient: out [n*L][P*P*C] (dtype) */
 int tmae_patchify(const float* imgs, void* out, int n, int C, int H, int W, int patch, int dtype, void* stream);
+/* MCM.unpatchify (MCM.py:524-546, "nhwpqc->nchpwq"): tokens [n*L][P*P*C] f32 -> imgs [n][C][H][W] f32,
+ * L = (H/P)*(W/P); the inverse of tmae_patchify(dtype f32). */
+int tmae_unpatchify(const float* tokens, float* imgs, int n, int C, int H, int W, int patch, void* stream);
 /* decoder_embed backward: gather the kept tokens' rows of the decoder gradient (off-by-one cls, MCM.py:664-672)
  * into tok_grad [n*ntok][D] (dtype) and the mask_token gradient (mask_part >= n*D floats) */
 int tmae_decoder_embed_bwd_gather(const float* dec_grad, const int64_t* ids_shuffle, void* tok_grad, int n, int ntok,

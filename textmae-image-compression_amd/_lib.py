@@ -200,6 +200,7 @@ SIGNATURES = {
     "tmae_eb_aux_bwd": [ctypes.POINTER(EBParams), P, P, P, I, I, P],
     "tmae_bpp_bwd": [P, P, P, LL, ctypes.c_double, P],
     "tmae_patchify": [P, P, I, I, I, I, I, I, P],
+    "tmae_unpatchify": [P, P, I, I, I, I, I, P],
     "tmae_decoder_embed_bwd_gather": [P, P, P, I, I, I, I, I, P, P, I, P],
     "tmae_add": [P, P, P, LL, P],
     "tmae_adam": [P, P, P, P, LL, F, F, F, F, F, I, P, P],

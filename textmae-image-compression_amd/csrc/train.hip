@@ -1513,6 +1513,53 @@ extern "C" int tmae_patchify(const float* imgs, void* out, int n, int C, int H, 
   TMAE_LAUNCH_CHECK("tmae_patchify");
 }
 
+// unpatchify ("nhwpqc -> nchpwq", MCM.py:524-546), the inverse of patchify_kernel<float>: a pure permutation.
+// P % 4 == 0: a lane owns 4 consecutive pixels of one (b, c, row) -- they lie in one patch row, so it reads 4 token
+// values C floats apart and stores 16 B; consecutive lanes continue along the image row.
+__global__ void __launch_bounds__(256)
+unpatchify4_kernel(const float* __restrict__ tok, float* __restrict__ img, int n, int C, int H, int W, int P) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int W4 = W / 4;
+  if (i >= (long long)n * C * H * W4) return;
+  const int x = 4 * (int)(i % W4);
+  long long r = i / W4;
+  const int y = (int)(r % H);
+  r /= H;
+  const int c = (int)(r % C), b = (int)(r / C);
+  const int G = W / P, L = (H / P) * G;
+  const int hy = y / P, py = y - hy * P, hx = x / P, px = x - hx * P;
+  const float* src = tok + ((size_t)b * L + hy * G + hx) * ((size_t)P * P * C) + (size_t)(py * P + px) * C + c;
+  store4(img + (((size_t)b * C + c) * H + y) * W + x, f32x4{src[0], src[C], src[2 * C], src[3 * C]});
+}
+
+// any other patch size (14): one pixel per lane, stores along the image row
+__global__ void __launch_bounds__(256)
+unpatchify1_kernel(const float* __restrict__ tok, float* __restrict__ img, int n, int C, int H, int W, int P) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n * C * H * W) return;
+  const int x = (int)(i % W);
+  long long r = i / W;
+  const int y = (int)(r % H);
+  r /= H;
+  const int c = (int)(r % C), b = (int)(r / C);
+  const int G = W / P, L = (H / P) * G;
+  const int hy = y / P, py = y - hy * P, hx = x / P, px = x - hx * P;
+  img[i] = tok[((size_t)b * L + hy * G + hx) * ((size_t)P * P * C) + (size_t)(py * P + px) * C + c];
+}
+
+extern "C" int tmae_unpatchify(const float* tokens, float* imgs, int n, int C, int H, int W, int patch, void* stream) {
+  TMAE_REQUIRE(tokens && imgs && n >= 0 && C > 0 && H > 0 && W > 0 && patch > 0, "tmae_unpatchify: bad arguments");
+  TMAE_REQUIRE(H % patch == 0 && W % patch == 0, "tmae_unpatchify: image %dx%d, patch %d", H, W, patch);
+  const bool vec = patch % 4 == 0 && ((uintptr_t)imgs & 15) == 0;  // W % 4 == 0 follows from W % patch == 0
+  const long long total = (long long)n * C * H * (vec ? W / 4 : W);
+  if (total == 0) return TMAE_OK;
+  TMAE_REQUIRE((total + 255) / 256 < (1ll << 31), "tmae_unpatchify: %lld work items exceed the grid", total);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  hipLaunchKernelGGL(vec ? unpatchify4_kernel : unpatchify1_kernel, grid, dim3(256), 0, (hipStream_t)stream, tokens,
+                     imgs, n, C, H, W, patch);
+  TMAE_LAUNCH_CHECK("tmae_unpatchify");
+}
+
 // decoder_embed backward gather (MCM.py:657-675): token k of image b sat at decoder row
 // 0 (k == 0) or 1 + ids_shuffle[b][k-1]; out[b*ntok + k] = dec_grad[b*(L+1) + row] (cast to the operand dtype)
 template <typename T>

@@ -12,6 +12,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from . import train_ops as T
 from .ops import _stream
 
 _PART = {}
@@ -58,6 +59,23 @@ class DistortionFn(torch.autograd.Function):
         _lib.call("tmae_distortion_bwd", x.data_ptr(), y.data_ptr(), P, H, W, d.data_ptr(), v.data_ptr(),
                   gout.data_ptr(), gx.data_ptr(), _stream())
         return gx, None
+
+
+class UnpatchifyFn(torch.autograd.Function):
+    """MCM.unpatchify (MCM.py:524-546) of preds [N, L, p*p*C] -> images [N, C, H, W] f32 on tmae_unpatchify;
+    the gradient w.r.t. preds is tmae_patchify (f32) of the images' gradient"""
+
+    @staticmethod
+    def forward(ctx, preds, patch, chans, H, W):
+        t = preds.float().contiguous()
+        ctx.patch, ctx.shape = patch, preds.shape
+        return T.unpatchify(t, torch.empty((t.shape[0], chans, H, W), dtype=torch.float32, device=t.device), patch)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.float().contiguous()
+        return T.patchify(g, torch.empty(ctx.shape, dtype=torch.float32, device=g.device), ctx.patch,
+                          torch.float32), None, None, None, None
 
 
 def ssim_l1_loss(x_hat, imgs):

@@ -3,8 +3,11 @@
 Same constructor arguments and defaults (MCM.py:34-52), same submodule names, so
 ``state_dict()`` keys, ``named_parameters()`` (``*.quantiles`` split, model_utils.py:67-90) and
 ``load_state_dict`` behave as in the reference; same call surface (``forward(imgs, total_scores)``
--> ``{"loss", "likelihoods", "x_hat"}``, ``aux_loss()``, ``from_state_dict``, ``patchify`` /
-``unpatchify``).
+-> ``{"loss", "likelihoods", "x_hat"}``, the staged ``forward_encoder(imgs, total_scores)`` ->
+``(x_remain, ids_restore)``, ``forward_decoder(x_remain, ids_restore)`` -> patch tokens and
+``forward_loss(imgs, preds)`` on patch tokens (or on the reconstruction itself), ``aux_loss()``,
+``from_state_dict``, ``patchify`` / ``unpatchify``).  The two stages run the same kernels as ``forward``'s
+encoder and decoder, without the entropy model; under autograd each is its own node (mcm_train.py).
 
 Underneath, ``forward`` never calls a PyTorch compute op on the hot path: it enqueues the gfx950
 kernels of libtmae.so on the current stream through a persistent workspace (``_Executor``), with
@@ -221,14 +224,70 @@ class MCM(CompressionModel):
             torch.zeros((), device=imgs.device),) * 3
         return {"loss": loss, "likelihoods": {"y": ylik, "z": zlik}, "x_hat": x_hat}
 
-    def forward_loss(self, imgs, x_hat):
-        """MCM.forward_loss (MCM.py:690-712): (1 - SSIM, L1, VGG16 feature loss).  The reference downloads
+    def _stage_trains(self, what, t, params, extra=False):
+        """common entry of forward_encoder / forward_decoder: the device check, then whether the stage takes its
+        training node (grad enabled and one of its parameters -- or `extra` -- requires grad, the rule of forward)"""
+        if not t.is_cuda:
+            raise ValueError(f"MCM.{what} runs on the MI355X kernels: move the model and inputs to the GPU")
+        return torch.is_grad_enabled() and (extra or any(p.requires_grad for p in params))
+
+    def forward_encoder(self, imgs, total_scores):
+        """MCM.forward_encoder (MCM.py:590-634) -> (x_remain f32 [N, K, E], ids_restore int64 [N, L]): ids, kept-patch
+        embedding, cls, encoder blocks, encoder_norm without the cls row; g_a / h_a do not run.  Under autograd its
+        own node with the HIP encoder backward (mcm_train._MCMEncFn)."""
+        from . import mcm_train
+
+        if self._stage_trains("forward_encoder", imgs, mcm_train.enc_params(self)):
+            return mcm_train.train_forward_encoder(self, imgs, total_scores)
+        with torch.no_grad():
+            return self._executor(imgs.shape[0], imgs.device).encode(imgs, total_scores)
+
+    def forward_decoder(self, x_remain, ids_restore):
+        """MCM.forward_decoder (MCM.py:636-688) -> preds f32 [N, L, p*p*in_chans], columns (py, px, c) as in the
+        reference.  x_remain [N, ntok, E] with 1 <= ntok <= L (mask tokens fill the other L + 1 - ntok rows; the
+        first token takes the cls row, the reference's off-by-one).  Under autograd (decoder parameters or x_remain
+        requiring gradients) its own node with the HIP decoder backward (mcm_train._MCMDecFn); ntok must then be
+        num_keep_patches."""
+        from . import mcm_train
+
+        train = self._stage_trains("forward_decoder", x_remain, mcm_train.dec_params(self),
+                                     extra=x_remain.requires_grad)
+        L, E = self.encoder_embed.num_patches, self.encoder_embed_dim
+        if x_remain.dim() != 3 or x_remain.shape[2] != E or not 1 <= x_remain.shape[1] <= L:
+            raise ValueError(f"forward_decoder: x_remain must be [N, ntok, E={E}] with 1 <= ntok <= L={L}, got "
+                             f"{tuple(x_remain.shape)}")
+        if tuple(ids_restore.shape) != (x_remain.shape[0], L):
+            raise ValueError(f"forward_decoder: ids_restore must be [N={x_remain.shape[0]}, L={L}], got "
+                             f"{tuple(ids_restore.shape)}")
+        if train:
+            return mcm_train.train_forward_decoder(self, x_remain, ids_restore)
+        with torch.no_grad():
+            return self._executor(x_remain.shape[0], x_remain.device).decode(x_remain, ids_restore)
+
+    def forward_loss(self, imgs, preds):
+        """MCM.forward_loss (MCM.py:690-712): (1 - SSIM, L1, VGG16 feature loss).  `preds` is either the reference's
+        argument, patch tokens [N, L, p*p*in_chans] (unpatchified here by tmae_unpatchify, differentiable w.r.t. the
+        tokens), or the reconstruction itself [N, in_chans, H, W] (what forward() passes).  The reference downloads
         torchvision's pretrained VGG16 on every call (vgg.py:14, 99); here the feature loss runs once local
         weights are given (load_vgg16, or the TMAE_VGG16_WEIGHTS file) and is 0 (with a one-time warning in
         training) without them."""
         from . import vgg
-        from .distortion import ssim_l1_loss
+        from .distortion import UnpatchifyFn, ssim_l1_loss
 
+        p, C = self.encoder_embed.patch_size[0], self.encoder_embed.proj.in_channels
+        L = self.encoder_embed.num_patches
+        if preds.dim() == 3:
+            if tuple(preds.shape[1:]) != (L, p * p * C) or preds.shape[0] != imgs.shape[0]:
+                raise ValueError(f"forward_loss: patch tokens must be [N={imgs.shape[0]}, L={L}, "
+                                 f"p*p*in_chans={p * p * C}], got {tuple(preds.shape)}")
+            if not preds.is_cuda:
+                raise ValueError("MCM.forward_loss runs on the MI355X kernels: move the model and inputs to the GPU")
+            x_hat = UnpatchifyFn.apply(preds, p, C, imgs.shape[2], imgs.shape[3])
+        elif preds.dim() == 4:
+            x_hat = preds
+        else:
+            raise ValueError(f"forward_loss takes patch tokens [N, L={L}, p*p*in_chans={p * p * C}] or images "
+                             f"[N, {C}, H, W], got a {preds.dim()}-D tensor {tuple(preds.shape)}")
         s, l1 = ssim_l1_loss(x_hat, imgs)
         net = self._vgg_net(imgs.device)
         if net is None:
@@ -517,6 +576,8 @@ class _Executor:
                          else m.decoder_pred.weight)
         self.b_dp = (m.decoder_pred.bias[perm.to(m.decoder_pred.bias.device)] if pred_cp
                      else m.decoder_pred.bias).detach().contiguous()
+        # the unpermuted (py, px, c) rows for the token-layout output of the decode stage
+        self.w_dp_tok = cast(m.decoder_pred.weight) if pred_cp else self.w_dp
 
     # ------------------------------------------------------------------ forward
     def _check_imgs(self, imgs):
@@ -603,10 +664,39 @@ class _Executor:
         shuf = ops.invert_permutation(ids_restore.to(self.device))
         return self._back(shuf, m.encoder_embed.proj.in_channels)
 
+    def encode(self, imgs, scores):
+        """the encoder stage alone (MCM.forward_encoder): -> (x_remain f32 [B, K, E], ids_restore), both fresh;
+        encoder_norm writes f32 whatever the operand dtype"""
+        m, B, K = self.m, self.batch, self.m.num_keep_patches
+        _, rest = self._enc_blocks(self._check_imgs(imgs), scores)
+        x = ops.layernorm(self.tok, m.encoder_norm.weight, m.encoder_norm.bias, m.encoder_norm.eps, torch.float32,
+                          rows=B * K, row_group=K, group_stride=K + 1, row_offset=1)
+        return x.view(B, K, -1), rest
+
+    def decode(self, x_remain, ids_restore):
+        """the decoder stage alone (MCM.forward_decoder) of x_remain [B, ntok, E]: -> preds f32 [B, L, p*p*C] (fresh)
+        in the reference's (py, px, c) column order, decoder_pred as a plain linear over the norm output"""
+        m, dt, B = self.m, self.dtype, self.batch
+        shuf = ops.invert_permutation(ids_restore.to(self.device))
+        x = x_remain.float().contiguous()
+        self._dec_blocks(x.view(-1, x.shape[2]), shuf, x.shape[1])
+        preds = ops.linear(self.dn, self.w_dp_tok, m.decoder_pred.bias.detach(), dt, out_dtype=torch.float32)
+        return preds.view(B, self.L, -1)
+
     def _front(self, imgs, scores):
         """encoder + g_a + h_a (MCM.py:590-634, 729-739): tokens -> Y32/YT -> Z; returns (ids_shuffle, ids_restore)"""
+        m, dt, B, K = self.m, self.dtype, self.batch, self.m.num_keep_patches
+        Te = K + 1
+        shuf, rest = self._enc_blocks(imgs, scores)
+        ops.layernorm(self.tok, m.encoder_norm.weight, m.encoder_norm.bias, m.encoder_norm.eps, dt, rows=B * K,
+                      row_group=K, group_stride=Te, row_offset=1, out=self.enc_out)
+        return self._front_lic(shuf, rest)
+
+    def _enc_blocks(self, imgs, scores):
+        """ids, kept-patch embedding, cls row and the encoder blocks (MCM.py:590-630) -> self.tok; returns
+        (ids_shuffle, ids_restore)"""
         m, dt, B = self.m, self.dtype, self.batch
-        E, M, K, P, g = m.encoder_embed_dim, m.latent_depth, m.num_keep_patches, self.P, self.g
+        E, K, P = m.encoder_embed_dim, m.num_keep_patches, self.P
         Te = K + 1
         # ---- encoder (MCM.py:590-634): ids on device, embed only the kept patches
         shuf, rest = ops.ids_shuffle(scores, K, m.sum_lanes)
@@ -615,9 +705,12 @@ class _Executor:
         ops.cls_rows(self.tok, m.cls_token.detach(), pos_e, B, Te, E)
         for w in self.enc_w:
             run_block(self.tok, w, B, Te, dt, self.enc_s)
-        ops.layernorm(self.tok, m.encoder_norm.weight, m.encoder_norm.bias, m.encoder_norm.eps, dt, rows=B * K,
-                      row_group=K, group_stride=Te, row_offset=1, out=self.enc_out)
+        return shuf, rest
 
+    def _front_lic(self, shuf, rest):
+        """g_a + h_a on the encoder output (MCM.py:729-739)"""
+        m, dt, B = self.m, self.dtype, self.batch
+        M, g = m.latent_depth, self.g
         # ---- g_a: 1x1 convs on the token matrix (tokens in ids_keep order = the g x g grid, MCM.py:729-735)
         x = self.enc_out
         for j, (w, b) in enumerate(self.ga_w):
@@ -644,8 +737,7 @@ class _Executor:
     def _back(self, shuf, in_chans):
         """g_s + decoder + unpatchify (MCM.py:636-688, 790-797) from YH; returns x_hat NCHW f32"""
         m, dt, B = self.m, self.dtype, self.batch
-        Dd, K, L, P = m.decoder_embed_dim, m.num_keep_patches, self.L, self.P
-        Td = L + 1
+        K, L, P = m.num_keep_patches, self.L, self.P
         # ---- g_s (MCM.py:790-792): transposed 1x1 convs back to E-dim tokens
         x = self.YH
         for j, (w, b) in enumerate(self.gs_w):
@@ -654,16 +746,24 @@ class _Executor:
             x = self.gs_buf[j]
 
         # ---- decoder (MCM.py:636-688): embed + unshuffle (+ off-by-one cls), blocks, norm, pred+unpatchify
+        self._dec_blocks(x, shuf, K)
+        x_hat = torch.empty((B, in_chans, self.img, self.img), dtype=torch.float32, device=self.device)
+        ops.decoder_pred(self.dn, self.w_dp, self.b_dp, x_hat, B, L, P, dt, channel_planar=self.pred_cp)
+        return x_hat
+
+    def _dec_blocks(self, x, shuf, ntok):
+        """decoder_embed of x [B*ntok, E] (f32 or the operand dtype) + unshuffle (+ off-by-one cls), mask rows,
+        blocks, decoder_norm without the cls rows (MCM.py:657-682) -> self.dn"""
+        m, dt, B = self.m, self.dtype, self.batch
+        Dd, L = m.decoder_embed_dim, self.L
+        Td = L + 1
         pos_d = m.decoder_pos_embed.detach()
-        ops.decoder_embed(x, self.w_de, m.decoder_embed.bias.detach(), pos_d, shuf, self.dec, B, K, L, dt)
-        ops.mask_rows(self.dec, m.mask_token.detach(), pos_d, shuf, B, L, K, Dd)
+        ops.decoder_embed(x, self.w_de, m.decoder_embed.bias.detach(), pos_d, shuf, self.dec, B, ntok, L, dt)
+        ops.mask_rows(self.dec, m.mask_token.detach(), pos_d, shuf, B, L, ntok, Dd)
         for w in self.dec_w:
             run_block(self.dec, w, B, Td, dt, self.dec_s)
         ops.layernorm(self.dec, m.decoder_norm.weight, m.decoder_norm.bias, m.decoder_norm.eps, dt, rows=B * L,
                       row_group=L, group_stride=Td, row_offset=1, out=self.dn)
-        x_hat = torch.empty((B, in_chans, self.img, self.img), dtype=torch.float32, device=self.device)
-        ops.decoder_pred(self.dn, self.w_dp, self.b_dp, x_hat, B, L, P, dt, channel_planar=self.pred_cp)
-        return x_hat
 
     # ------------------------------------------------------------------ Gaussian-conditional slice steps
     # Each is called with (i0, nbs, mu, sigma, ms_stride): slices i0..i0+nbs-1, mu/sigma device addresses

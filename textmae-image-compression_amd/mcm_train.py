@@ -511,6 +511,9 @@ class TrainExec(_VitTrainBase):
         self.sw = m.latent_depth // m.num_slices
         self.ms = m.num_slices // 2
         self.mid = [l.out_channels for l in _convs(m.cc_transform_mean[0])]
+        # forward counters of the two ViT stages: a staged backward (_MCMEncFn / _MCMDecFn) refuses activations a later
+        # forward of that stage -- or a whole forward -- replaced
+        self.enc_gen = self.dec_gen = 0
         self._layout()
 
     def _grad_order(self):
@@ -551,15 +554,9 @@ class TrainExec(_VitTrainBase):
 
     # ------------------------------------------------------------------ forward
     def forward(self, imgs, scores, noise):
-        m, dt, B = self.m, self.dtype, self.batch
-        E, K, P, g = m.encoder_embed_dim, m.num_keep_patches, self.P, self.g
-        M, N, S, hz = m.latent_depth, m.hyperprior_depth, m.num_slices, self.hz
-        Te, Td = K + 1, self.L + 1
-        imgs = imgs.float().contiguous()
-        if imgs.shape[1:] != (m.encoder_embed.proj.in_channels, self.img, self.img):
-            raise ValueError(f"Input image size {tuple(imgs.shape[2:])} doesn't match model ({self.img})")
-        self.imgs = imgs
-        self.w.refresh()  # one launch for every weight copy the last optimizer step made stale
+        m, B, g = self.m, self.batch, self.g
+        M, N, hz = m.latent_depth, m.hyperprior_depth, self.hz
+        imgs = self._begin(imgs)
         if noise is not None:
             self.z_noise, self.y_noise = (t.float().contiguous() for t in noise)
         elif not m.training:  # eval semantics: round(x - median) + median / round(y - mu) + mu
@@ -567,9 +564,29 @@ class TrainExec(_VitTrainBase):
         else:
             self.z_noise = torch.empty((B, N, hz, hz), device=self.device).uniform_(-0.5, 0.5)
             self.y_noise = torch.empty((B, M, g, g), device=self.device).uniform_(-0.5, 0.5)
-        W = self.w
+        self.enc_out = self.enc_fwd(imgs, scores)
+        self._lic_fwd(self.enc_out)
+        x_hat = self.dec_fwd(self.gs_out)
+        return x_hat, self.YLIK, self.ZLIK
 
-        # ---- encoder (MCM.py:590-634): masking ids, kept-patch embedding, cls, blocks, norm
+    def _begin(self, imgs):
+        """what every forward entry starts with: the image check and the weight copies' refresh"""
+        m = self.m
+        imgs = imgs.float().contiguous()
+        if imgs.shape[1:] != (m.encoder_embed.proj.in_channels, self.img, self.img):
+            raise ValueError(f"Input image size {tuple(imgs.shape[2:])} doesn't match model ({self.img})")
+        self.imgs = imgs
+        self.w.refresh()  # one launch for every weight copy the last optimizer step made stale
+        return imgs
+
+    def enc_fwd(self, imgs, scores, out_dtype=None):
+        """forward_encoder (MCM.py:590-634) of imgs (after _begin): masking ids, kept-patch embedding, cls, blocks,
+        encoder_norm without the cls rows -> [B*K, E] in out_dtype (the compute dtype by default); keeps the
+        encoder's activations and the shuffle for the backward"""
+        m, dt, B, W = self.m, self.dtype, self.batch, self.w
+        E, K, P = m.encoder_embed_dim, m.num_keep_patches, self.P
+        Te = K + 1
+        self.enc_gen += 1
         shuf, rest = ops.ids_shuffle(scores, K, m.sum_lanes)
         self.shuf, self.rest = shuf, rest
         pos_e = m.encoder_pos_embed.detach()
@@ -582,9 +599,14 @@ class TrainExec(_VitTrainBase):
         for blk in m.encoder_blocks:
             tok = self._block_fwd(blk, tok, B, Te)
         self.tok_last = tok
-        enc_out = ops.layernorm(tok, m.encoder_norm.weight, m.encoder_norm.bias, m.encoder_norm.eps, dt, rows=B * K,
-                                row_group=K, group_stride=Te, row_offset=1)
-        self.enc_out = enc_out
+        return ops.layernorm(tok, m.encoder_norm.weight, m.encoder_norm.bias, m.encoder_norm.eps, out_dtype or dt,
+                             rows=B * K, row_group=K, group_stride=Te, row_offset=1)
+
+    def _lic_fwd(self, enc_out):
+        """g_a, h_a, the entropy models, h_s, the slice loop and g_s (MCM.py:729-792) -> self.gs_out"""
+        m, dt, B, W = self.m, self.dtype, self.batch, self.w
+        g = self.g
+        M, N, hz = m.latent_depth, m.hyperprior_depth, self.hz
 
         # ---- g_a (MCM.py:735)
         x = enc_out
@@ -660,7 +682,15 @@ class TrainExec(_VitTrainBase):
             x = h
         self.gs_out = x
 
-        # ---- decoder (MCM.py:636-688)
+    def dec_fwd(self, x, tokens=False):
+        """forward_decoder (MCM.py:636-688) of x [B*K, E] (compute dtype) under self.shuf: embed + unshuffle (+ the
+        off-by-one cls), blocks, norm, then decoder_pred fused with unpatchify -> x_hat f32 [B, C, H, W], or
+        (tokens) as a plain linear -> preds f32 [B*L, p*p*C] in the reference's (py, px, c) column order"""
+        m, dt, B, W = self.m, self.dtype, self.batch, self.w
+        K, P, shuf = m.num_keep_patches, self.P, self.shuf
+        Td = self.L + 1
+        self.dec_gen += 1
+        self.gs_out = x
         Dd, L = m.decoder_embed_dim, self.L
         pos_d = m.decoder_pos_embed.detach()
         dec = torch.empty((B * Td, Dd), dtype=torch.float32, device=self.device)
@@ -673,9 +703,13 @@ class TrainExec(_VitTrainBase):
         self.dec_last = dec
         self.dn = ops.layernorm(dec, m.decoder_norm.weight, m.decoder_norm.bias, m.decoder_norm.eps, dt, rows=B * L,
                                 row_group=L, group_stride=Td, row_offset=1)
-        x_hat = torch.empty((B, imgs.shape[1], self.img, self.img), dtype=torch.float32, device=self.device)
+        if tokens:
+            return ops.linear(self.dn, W.nt(m.decoder_pred.weight), m.decoder_pred.bias.detach(), dt,
+                              out_dtype=torch.float32)
+        x_hat = torch.empty((B, m.encoder_embed.proj.in_channels, self.img, self.img), dtype=torch.float32,
+                            device=self.device)
         ops.decoder_pred(self.dn, W.nt(m.decoder_pred.weight), m.decoder_pred.bias.detach(), x_hat, B, L, P, dt)
-        return x_hat, self.YLIK, self.ZLIK
+        return x_hat
 
     def _h_s_fwd(self, seq, out_final, ld_final):
         dt, W, B = self.dtype, self.w, self.batch
@@ -1006,44 +1040,17 @@ class TrainExec(_VitTrainBase):
     def backward(self, dxhat, dylik, dzlik, gflat, sync=None):
         """full reverse pass; every parameter's gradient lands in gflat (views per self.offsets)"""
         m, dt, W, B = self.m, self.dtype, self.w, self.batch
-        E, K, P, g = m.encoder_embed_dim, m.num_keep_patches, self.P, self.g
-        M, N, S, hz, L = m.latent_depth, m.hyperprior_depth, m.num_slices, self.hz, self.L
-        Dd = m.decoder_embed_dim
-        Te, Td = K + 1, L + 1
+        P, M, N, hz, L = self.P, m.latent_depth, m.hyperprior_depth, self.hz, self.L
         Mp = self.Mp
-        self.gflat = gflat
-        self.sync = sync
-        if sync is not None:
-            sync.attach(gflat)
-        self._side_begin()
+        self.bwd_begin(gflat, sync)
         G = self.grad
         dxhat = dxhat.float().contiguous() if dxhat is not None else torch.zeros_like(self.imgs)
         dylik = dylik.float().contiguous() if dylik is not None else None
         dzlik = dzlik.float().contiguous() if dzlik is not None else None
 
-        # ---- decoder_pred + unpatchify (MCM.py:683-686, 797)
+        # ---- unpatchify (MCM.py:797), decoder
         dP = T.patchify(dxhat, self._e(B * L, dxhat.shape[1] * P * P), P, dt)
-        npred = dP.shape[1]
-        self._wg(dP, self.dn, npred, Dd, B * L, G(m.decoder_pred.weight), dt, bias=G(m.decoder_pred.bias))
-        ddn = torch.empty((B * L, Dd), dtype=torch.float32, device=self.device)
-        T.dgrad_linear(dP, W.t(m.decoder_pred.weight), B * L, npred, Dd, dt, out=ddn)
-        ddec = self._z(B * Td, Dd)
-        ddec_op = ddec if dt == torch.float32 else self._z(B * Td, Dd, dtype=dt)
-        T.layernorm_bwd(self.dec_last, m.decoder_norm.weight, ddn, ddec, B * L, Dd, m.decoder_norm.eps,
-                        G(m.decoder_norm.weight), G(m.decoder_norm.bias), dxop=None if dt == torch.float32 else ddec_op,
-                        row_group=L, group_stride=Td, row_offset=1)
-        self._ready(m.decoder_norm.bias)
-        for blk, s in zip(reversed(m.decoder_blocks), reversed(self.dec)):
-            ddec, ddec_op = self._block_bwd(blk, s, ddec, ddec_op, B, Td)
-            self._ready(_block_params(blk)[-1])
-
-        # ---- decoder_embed + mask tokens (MCM.py:657-675)
-        dtok = self._e(Mp, Dd)
-        T.decoder_embed_bwd_gather(ddec, self.shuf, dtok, B, K, L, Dd, dt, dmask=G(m.mask_token).view(-1))
-        self._wg(dtok, self.gs_out, Dd, E, Mp, G(m.decoder_embed.weight), dt, bias=G(m.decoder_embed.bias))
-        d = self._e(Mp, E)
-        T.dgrad_linear(dtok, W.t(m.decoder_embed.weight), Mp, Dd, E, dt, out=d)
-        self._ready(m.mask_token)
+        d = self.dec_bwd(dP)
 
         # ---- g_s
         gs = [l for l in m.g_s if isinstance(l, nn.ConvTranspose2d)]
@@ -1110,9 +1117,17 @@ class TrainExec(_VitTrainBase):
                 dx = torch.empty((Mp, cin), dtype=torch.float32, device=self.device)
                 T.dgrad_linear(d, W.t(l.weight), Mp, cout, cin, dt, out=dx)
             d = dx
-        denc = d
         self._ready(ga[0].bias)
+        self.enc_bwd(d)
+        self._side_join()
 
+    def enc_bwd(self, denc):
+        """encoder backward (MCM.py:590-634) from denc f32 [B*K, E], the gradient of encoder_norm's output without
+        the cls rows: every encoder parameter's gradient"""
+        m, dt, B = self.m, self.dtype, self.batch
+        E, K = m.encoder_embed_dim, m.num_keep_patches
+        Te = K + 1
+        G = self.grad
         # ---- encoder norm (drops cls, MCM.py:631-632) + blocks
         dt_tok = self._z(B * Te, E)
         dt_op = dt_tok if dt == torch.float32 else self._z(B * Te, E, dtype=dt)
@@ -1130,7 +1145,44 @@ class TrainExec(_VitTrainBase):
         T.colsum(dt_tok, B * K, E, G(m.encoder_embed.proj.bias), row_group=K, group_stride=Te, row_offset=1)
         T.colsum(dt_tok, B, E, G(m.cls_token).view(-1), row_group=1, group_stride=Te, row_offset=0)
         self._ready(m.cls_token)
-        self._side_join()
+
+    def bwd_begin(self, gflat, sync=None):
+        self.gflat, self.sync = gflat, sync
+        if sync is not None:
+            sync.attach(gflat)
+        self._side_begin()
+
+    def dec_bwd(self, dP, out_f32=False):
+        """decoder backward (MCM.py:636-688) from dP [B*L, p*p*C] (compute dtype), the gradient of decoder_pred's
+        token-layout output: every decoder parameter's gradient; -> the gradient of the decoder's input tokens
+        [B*K, E] in the compute dtype (g_s goes on with it) or, out_f32, in f32"""
+        m, dt, W, B = self.m, self.dtype, self.w, self.batch
+        E, K, L, Dd = m.encoder_embed_dim, m.num_keep_patches, self.L, m.decoder_embed_dim
+        Td, Mp = L + 1, self.Mp
+        G = self.grad
+        # ---- decoder_pred (MCM.py:683-686)
+        npred = dP.shape[1]
+        self._wg(dP, self.dn, npred, Dd, B * L, G(m.decoder_pred.weight), dt, bias=G(m.decoder_pred.bias))
+        ddn = torch.empty((B * L, Dd), dtype=torch.float32, device=self.device)
+        T.dgrad_linear(dP, W.t(m.decoder_pred.weight), B * L, npred, Dd, dt, out=ddn)
+        ddec = self._z(B * Td, Dd)
+        ddec_op = ddec if dt == torch.float32 else self._z(B * Td, Dd, dtype=dt)
+        T.layernorm_bwd(self.dec_last, m.decoder_norm.weight, ddn, ddec, B * L, Dd, m.decoder_norm.eps,
+                        G(m.decoder_norm.weight), G(m.decoder_norm.bias), dxop=None if dt == torch.float32 else ddec_op,
+                        row_group=L, group_stride=Td, row_offset=1)
+        self._ready(m.decoder_norm.bias)
+        for blk, s in zip(reversed(m.decoder_blocks), reversed(self.dec)):
+            ddec, ddec_op = self._block_bwd(blk, s, ddec, ddec_op, B, Td)
+            self._ready(_block_params(blk)[-1])
+
+        # ---- decoder_embed + mask tokens (MCM.py:657-675)
+        dtok = self._e(Mp, Dd)
+        T.decoder_embed_bwd_gather(ddec, self.shuf, dtok, B, K, L, Dd, dt, dmask=G(m.mask_token).view(-1))
+        self._wg(dtok, self.gs_out, Dd, E, Mp, G(m.decoder_embed.weight), dt, bias=G(m.decoder_embed.bias))
+        d = torch.empty((Mp, E), dtype=torch.float32, device=self.device) if out_f32 else self._e(Mp, E)
+        T.dgrad_linear(dtok, W.t(m.decoder_embed.weight), Mp, Dd, E, dt, out=d)
+        self._ready(m.mask_token)
+        return d
 
     def _eb_grads(self, eb):
         from ._lib import EBParams
@@ -1520,6 +1572,108 @@ class _MCMTrainFn(torch.autograd.Function):
                 off = ex.offsets[id(p)]
                 out.append(gflat[off:off + p.numel()].view(p.shape))
         return (None, None, None, None, *out)
+
+
+# ---------------------------------------------------------------------- forward_encoder / forward_decoder alone
+# (MCM.py:590-688 as separate nn.Module calls under autograd, like mae_train.py's: each is its own node over its own
+# parameters; the executor keeps one set of activations per stage, so a stage's backward must come before that
+# stage's next forward -- checked by the executor's forward counters.  No DP hand-offs: sync stays None.)
+def enc_params(m):
+    out = [m.encoder_norm.weight, m.encoder_norm.bias]
+    for blk in m.encoder_blocks:
+        out += _block_params(blk)
+    return out + [m.encoder_embed.proj.weight, m.encoder_embed.proj.bias, m.cls_token]
+
+
+def dec_params(m):
+    out = [m.decoder_pred.weight, m.decoder_pred.bias, m.decoder_norm.weight, m.decoder_norm.bias,
+           m.decoder_embed.weight, m.decoder_embed.bias, m.mask_token]
+    for blk in m.decoder_blocks:
+        out += _block_params(blk)
+    return out
+
+
+def _param_grads(ex, params, gflat):
+    return [gflat[ex.offsets[id(p)]:ex.offsets[id(p)] + p.numel()].view(p.shape) if p.requires_grad else None
+            for p in params]
+
+
+class _MCMEncFn(torch.autograd.Function):
+    """MCM.forward_encoder: (imgs, scores, *encoder params) -> (x_remain f32 [B, K, E], ids_restore)"""
+
+    @staticmethod
+    def forward(ctx, ex, imgs, scores, *params):
+        x = ex.enc_fwd(ex._begin(imgs), scores, out_dtype=torch.float32)
+        ctx.ex, ctx.params, ctx.gen = ex, params, ex.enc_gen
+        ctx.mark_non_differentiable(ex.rest)
+        return x.view(ex.batch, ex.m.num_keep_patches, -1), ex.rest
+
+    @staticmethod
+    def backward(ctx, dx, drest):
+        ex, params = ctx.ex, ctx.params
+        if ex.enc_gen != ctx.gen:
+            raise RuntimeError("forward_encoder (or forward) ran again on this model before this backward: its saved "
+                               "activations are gone (backward each forward_encoder before the next)")
+        gflat = ex.grads_buffer(any(p.grad is not None for p in params if p.requires_grad))
+        ex.bwd_begin(gflat)
+        ex.enc_bwd(dx.float().contiguous().view(ex.Mp, -1))
+        ex._side_join()
+        return (None, None, None, *_param_grads(ex, params, gflat))
+
+
+class _MCMDecFn(torch.autograd.Function):
+    """MCM.forward_decoder: (x_remain [B, K, E], *decoder params) -> preds f32 [B, L, p*p*C] (ids_restore fixed)"""
+
+    @staticmethod
+    def forward(ctx, ex, ids_restore, x, *params):
+        ex.rest = ids_restore
+        ex.shuf = ops.invert_permutation(ids_restore)
+        ex.w.refresh()  # (a no-op after forward_encoder's)
+        preds = ex.dec_fwd(ex._cast(x.float().contiguous().view(ex.Mp, -1)), tokens=True)
+        ctx.ex, ctx.params, ctx.gen, ctx.xshape = ex, params, ex.dec_gen, x.shape
+        return preds.view(ex.batch, ex.L, -1)
+
+    @staticmethod
+    def backward(ctx, dpreds):
+        ex, params = ctx.ex, ctx.params
+        if ex.dec_gen != ctx.gen:
+            raise RuntimeError("forward_decoder (or forward) ran again on this model before this backward: its saved "
+                               "activations are gone (backward each forward_decoder before the next)")
+        gflat = ex.grads_buffer(any(p.grad is not None for p in params if p.requires_grad))
+        ex.bwd_begin(gflat)
+        dP = ex._cast(dpreds.float().contiguous().view(ex.batch * ex.L, -1))  # the node starts at dP: no patchify
+        dx = ex.dec_bwd(dP, out_f32=True)
+        ex._side_join()
+        return (None, None, dx.view(ctx.xshape), *_param_grads(ex, params, gflat))
+
+
+def _exec_for(m, B, device):
+    if getattr(m, "grad_sync", None) is not None:
+        raise RuntimeError("MCM.forward_encoder / forward_decoder under autograd run without gradient all-reduce: "
+                           "bucketed data parallel (grad_sync) covers forward() only")
+    dt = m.compute_dtype
+    if torch.is_autocast_enabled() and dt == torch.float32:
+        dt = torch.bfloat16
+    ex = getattr(m, "_train_exec", None)
+    if ex is None or ex.batch != B or ex.dtype != dt or ex.device != device:
+        ex = m._train_exec = TrainExec(m, B, dt, device)
+    return ex
+
+
+def train_forward_encoder(m, imgs, scores):
+    """MCM.forward_encoder with autograd: (x_remain f32 [N, K, E], ids_restore)"""
+    ex = _exec_for(m, imgs.shape[0], imgs.device)
+    return _MCMEncFn.apply(ex, imgs, scores, *enc_params(m))
+
+
+def train_forward_decoder(m, x, ids_restore):
+    """MCM.forward_decoder with autograd: preds f32 [N, L, p*p*C] (gradients to x and the decoder's parameters)"""
+    n, ntok, _ = x.shape
+    if ntok != m.num_keep_patches:
+        raise ValueError(f"forward_decoder under autograd takes num_keep_patches={m.num_keep_patches} tokens per image "
+                         f"(the training workspaces are sized by it), got {ntok}")
+    ex = _exec_for(m, n, x.device)
+    return _MCMDecFn.apply(ex, ids_restore.to(x.device).to(torch.int64).contiguous(), x, *dec_params(m))
 
 
 class BppFn(torch.autograd.Function):

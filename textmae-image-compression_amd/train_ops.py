@@ -255,6 +255,17 @@ def patchify(imgs, out, patch, dtype):
     return out
 
 
+def unpatchify(tokens, imgs, patch):
+    """imgs [n][C][H][W] f32 <- tokens [n*L][P*P*C] f32 (MCM.unpatchify; the inverse of patchify(dtype f32))"""
+    n, C, H, W = imgs.shape
+    if tokens.dtype != torch.float32 or imgs.dtype != torch.float32:
+        raise ValueError("unpatchify: f32 tensors only")
+    if not tokens.is_contiguous() or not imgs.is_contiguous() or tokens.numel() != imgs.numel():
+        raise ValueError(f"unpatchify: tokens {tuple(tokens.shape)} do not fill images {tuple(imgs.shape)}")
+    _lib.call("tmae_unpatchify", tokens.data_ptr(), imgs.data_ptr(), n, C, H, W, patch, _stream())
+    return imgs
+
+
 def decoder_embed_bwd_gather(dec_grad, ids, tok_grad, n, ntok, L, D, dtype, dmask=None, accumulate=False):
     part = scratch(dec_grad.device, n * D, slot=2) if dmask is not None else None
     _lib.call("tmae_decoder_embed_bwd_gather", dec_grad.data_ptr(), ids.data_ptr(), tok_grad.data_ptr(), n, ntok, L, D,

@@ -566,8 +566,16 @@ int tmae_distortion_bwd(const float* x, const float* y, int P, int H, int W, con
 
 /* diagnostics (no device work): writes into out[len] the name of the MFMA GEMM variant that
  * tmae_linear_fwd / tmae_conv3x3 launch for an M x N x K problem batched `batch` times (tile shape,
- * waves per workgroup, LDS ring), e.g. "ring<bf16,256x256,8w,BK32x4>". */
+ * waves per workgroup, K-step x LDS stages actually launched), e.g. "glds<bf16,32x64,4w,BK64x4>". */
 int tmae_gemm_plan(int M, int N, int K, int batch, int dtype, char* out, int len);
+
+/* test hook (host only, no device work): every MFMA GEMM launch of this process takes tile `index` of the
+ * candidate list instead of the chooser's pick -- 0: 256x256, 1: 128x128, 2: 64x128, 3: 32x128, 4: 64x64,
+ * 5: 32x64, 6: 256x192, 7: 128x160, 8: 128x192 (weight rows x token rows) -- where the path instantiates it
+ * (0, 6, 7, 8: bf16 LDS-DMA launches only; elsewhere the chooser still picks).  -1, the default, restores the
+ * chooser.  Returns the previous value; tmae_gemm_plan reflects it.  Not synchronised: set it from one thread,
+ * between launches. */
+int tmae_gemm_force_tile(int index);
 
 #ifdef __cplusplus
 }

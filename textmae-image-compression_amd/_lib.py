@@ -216,7 +216,8 @@ VALUE_FUNCS = {"tmae_wgrad_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_wgrad_workspace_nb": ([I, I, I, I, I, I], ctypes.c_longlong),
                "tmae_metrics_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_image_scores_workspace": ([I, I, I, I], ctypes.c_longlong),
-               "tmae_qkv_attn_supported": ([I, I, I], ctypes.c_int)}
+               "tmae_qkv_attn_supported": ([I, I, I], ctypes.c_int),
+               "tmae_gemm_force_tile": ([I], ctypes.c_int)}
 
 _lib = None
 

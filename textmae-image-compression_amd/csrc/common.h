@@ -72,7 +72,7 @@ __device__ __forceinline__ float gelu_erf(float x) {
 
 // GELU for bf16 outputs: x * sigmoid(x (a + b x^2 + c x^4)), coefficients fitted to the erf GELU by
 // minimax over [-10, 10] (x clamped there inside the sigmoid, saturated beyond): |error| <= 2.6e-5 absolute, far below bf16 resolution of the stored value
-// (half an ulp is 2^-9 relative).  One v_exp + one v_rcp + five FMA-class ops against gelu_erf's
+// (half an ulp is 2^-9 .. 2^-8 relative).  One v_exp + one v_rcp + five FMA-class ops against gelu_erf's
 // fifteen: the GELU of the fc1 / decoder-fc1 epilogues was 14 us of a 74 us launch.  The log2(e)
 // of exp is folded into the coefficients.  Large |x|: exp2 -> inf gives 0 (x < 0), exp2 -> 0 gives x.
 __device__ __forceinline__ float gelu_bf16out(float x) {

@@ -397,7 +397,16 @@ extern "C" int tmae_decoder_pred_fwd(const void* x, const void* w, const float* 
 extern "C" int tmae_gemm_plan(int M, int N, int K, int batch, int dtype, char* out, int len) {
   TMAE_REQUIRE(out != nullptr && len > 0 && M >= 0 && N >= 0 && K >= 0 && batch >= 1, "tmae_gemm_plan: bad arguments");
   const bool bf = dtype == TMAE_BF16;
-  const TileChoice tc = choose_tile(M, N, K, batch, bf);
-  snprintf(out, len, "glds<%s,%dx%d,%dw,BK%dx2>", bf ? "bf16" : "f32", tc.bn, tc.bm, tc.nw, bf ? 64 : 32);
+  const TileChoice tc = choose_tile(M, N, K, batch, bf);  // honours tmae_gemm_force_tile like every launch
+  const int stages = gemm_ring_stages(bf ? 2 : 4, tc.bn, tc.bm, tc.nw, K);
+  snprintf(out, len, "glds<%s,%dx%d,%dw,BK%dx%d>", bf ? "bf16" : "f32", tc.bn, tc.bm, tc.nw, bf ? 64 : 32, stages);
   return TMAE_OK;
+}
+
+// test hook: the tile every launch_gemm takes (index into kTileCand) until reset with -1
+int g_tmae_gemm_force_tile = -1;
+extern "C" int tmae_gemm_force_tile(int index) {
+  const int prev = g_tmae_gemm_force_tile;
+  g_tmae_gemm_force_tile = (index >= 0 && index < kNumTiles) ? index : -1;
+  return prev;
 }

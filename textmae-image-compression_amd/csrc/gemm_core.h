@@ -792,13 +792,17 @@ static inline bool tile_bf16_only(int i) { return kTileCand[i][2] == 8 || i >= 7
 // forced (enc fc1 65.0 vs 63.5 us, dec fc1 66.2 vs 57.3) and -6.5 % on the forward when offered to the chooser
 // (profiles/r04/c9_*): dropped; the partial token-side DMA round it needed stays in the kernel.
 // Tuning experiments override these with a variant build (tools/build_variant.sh -DTMAE_GEMM_TILE=<i>).
+// Tests force a tile at run time instead: tmae_gemm_force_tile (include/tmae.h) sets this index into kTileCand,
+// -1 = the chooser.  One copy for every translation unit, defined in gemm.hip.  Like the macro it only replaces
+// the score: a tile the path does not instantiate is ignored, and every launch keeps its own eligibility checks.
+extern int g_tmae_gemm_force_tile;
 #ifndef TMAE_GEMM_TILE
 #define TMAE_GEMM_TILE -1
 #endif
 static inline TileChoice choose_tile(int M, int N, int K, int batch, bool allow_big) {
   const double kf = 1.0 + 0.12 * std::log2(std::max(K, 768) / 768.0);
   const double eff[kNumTiles] = {1.10 * kf, 1.0, 0.86, 0.70, 0.72, 0.55, 1.08 * kf, 1.22, 1.25};
-  constexpr int forced = TMAE_GEMM_TILE;
+  const int forced = g_tmae_gemm_force_tile >= 0 ? g_tmae_gemm_force_tile : TMAE_GEMM_TILE;
   if (forced >= 0 && forced < kNumTiles && (allow_big || !tile_bf16_only(forced)))
     return TileChoice{kTileCand[forced][0], kTileCand[forced][1], kTileCand[forced][2]};
   double best = -1.0;
@@ -817,18 +821,27 @@ static inline TileChoice choose_tile(int M, int N, int K, int batch, bool allow_
   return tc;
 }
 
+// LDS stages of the LDS-DMA kernel for a tile and a K (the one rule launch_one and tmae_gemm_plan share): small
+// tiles over a long K (>= 8 K-steps) take a 4-stage (<= 160 LDS rows) or 3-stage (<= 213 rows) ring: either stays
+// within 80 KB, two workgroups per CU (LIC conv family 1129 -> 1095 us per forward).  2-byte
+// operands on the 4-wave tiles only; everything else the 2-stage ring.
+static constexpr int kGemmAnyK = 1 << 30;  // a K past every threshold: the deepest ring a tile can get
+static constexpr int gemm_ring_stages(int elt_bytes, int bn, int bm, int nw, int K) {
+  const int dns = (bn + bm) * 128 * 4 <= 80 * 1024 ? 4 : (bn + bm) * 128 * 3 <= 80 * 1024 ? 3 : 2;
+  const bool deep_ok = elt_bytes == 2 && nw == 4 && dns > 2;
+  const int bke = 128 / elt_bytes;  // elements per K-step (128-B LDS rows)
+  return deep_ok && (K + bke - 1) / bke >= 8 ? dns : 2;
+}
+
 template <bool GLDS, typename T, int BN, int BM, int WGN, int NW, class WS, class XS, class EPI>
 static int launch_one(const char* name, const WS& ws, const XS& xs, const EPI& epi, int M, int N, int K, int n1,
                       int n2, hipStream_t st) {
   const int tiles = ceil_div(N, BN) * ceil_div(M, BM);
   if (tiles == 0 || n1 * n2 == 0) return TMAE_OK;
   if constexpr (GLDS) {
-    // small tiles over a long K take a 4-stage (<= 160 LDS rows) or 3-stage (<= 213 rows) ring: either stays
-    // within 80 KB, two workgroups per CU (LIC conv family 1129 -> 1095 us per forward)
-    constexpr int DNS = (BN + BM) * 128 * 4 <= 80 * 1024 ? 4 : (BN + BM) * 128 * 3 <= 80 * 1024 ? 3 : 2;
-    constexpr bool deep_ok = sizeof(T) == 2 && NW == 4 && DNS > 2;
-    if constexpr (deep_ok) {
-      if (ceil_div(K, 8 * Elt<T>::EPC) >= 8) {
+    constexpr int DNS = gemm_ring_stages(sizeof(T), BN, BM, NW, kGemmAnyK);
+    if constexpr (DNS > 2) {
+      if (gemm_ring_stages(sizeof(T), BN, BM, NW, K) == DNS) {
         hipLaunchKernelGGL((gemm_glds_kernel<T, BN, BM, WGN, NW, WS, XS, EPI, DNS>), dim3(tiles, n1 * n2),
                            dim3(64 * NW), 0, st, ws, xs, epi, M, N, K, n2);
         TMAE_LAUNCH_CHECK(name);

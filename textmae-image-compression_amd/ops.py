@@ -6,6 +6,7 @@ the library never allocates) unless an `out=` buffer is passed.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -17,7 +18,7 @@ from ._lib import ACT_GELU, ACT_NONE, TMAE_BF16, TMAE_F32, ConvArgs, EBParams, L
 __all__ = [
     "ids_shuffle", "layernorm", "linear", "linear_residual", "patch_embed", "cls_rows", "mha", "decoder_embed",
     "mask_rows", "decoder_pred", "conv3x3", "lic_stack", "pack_lic_stack_weight", "lic_stack_fits", "gc_slices", "eb_likelihood", "eb_aux_loss",
-    "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "dtype_code", "gc_slices_code", "gc_indexes",
+    "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "dtype_code", "gc_slices_code", "gc_indexes",
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "mae_loss", "TMAE_F32", "TMAE_BF16", "ACT_NONE", "ACT_GELU",
 ]
@@ -57,6 +58,23 @@ def gemm_plan(M: int, N: int, K: int, dtype: torch.dtype, batch: int = 1) -> str
     buf = ctypes.create_string_buffer(96)
     _lib.call("tmae_gemm_plan", M, N, K, batch, dtype_code(dtype), buf, len(buf))
     return buf.value.decode()
+
+
+# tmae_gemm_force_tile's candidate list (gemm_core.h kTileCand): weight rows x token rows of a workgroup's tile
+GEMM_TILES = ((256, 256), (128, 128), (64, 128), (32, 128), (64, 64), (32, 64), (256, 192), (128, 160), (128, 192))
+
+
+@contextlib.contextmanager
+def force_gemm_tile(index: int):
+    """Test hook: every MFMA GEMM launched inside the block takes tile GEMM_TILES[index] where its path has it
+    (tmae_gemm_force_tile); -1 = the chooser.  The previous value is restored on exit."""
+    if not -1 <= index < len(GEMM_TILES):
+        raise ValueError(f"force_gemm_tile: index {index} outside -1..{len(GEMM_TILES) - 1}")
+    prev = _lib.value("tmae_gemm_force_tile", index)
+    try:
+        yield
+    finally:
+        _lib.value("tmae_gemm_force_tile", prev)
 
 
 # --------------------------------------------------------------------------------------- masking

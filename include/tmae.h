@@ -356,6 +356,45 @@ int tmae_rans_decode_with_indexes(void* handle, const int32_t* indexes, long lon
                                   int32_t* out);
 int tmae_rans_decoder_destroy(void* handle);
 
+/* ---------------------------------------------------------------- entropy coding, per-image streams on the device
+ * (MCM.compress_batch / decompress_batch; csrc/rans_device.hip).  Same format as the host coder above: stream b
+ * is byte for byte what tmae_rans_encode_with_indexes + flush write for stream b's symbols alone.
+ * Layout, both directions: stream b codes segments j = 0..nseg-1 in order, segment j = seg_len consecutive int32
+ * at base + j * seg_stride + b * stream_stride (elements; symbols and indexes have their own strides).  Tables
+ * are DEVICE int32 arrays with the values of the host tables; they are validated where they are built
+ * (EntropyModel.device_tables), not per launch.  One wave per stream.
+ * status[b] (0 = fine): 1 output slab / dense buffer too small, 2 symbol search outside the row, 3 escape longer
+ * than 8 digits, 4 read past the stream's length, 5 table index outside [0, ncdf), 6 stream offset / length /
+ * position outside the word buffer.  A stream with a status stops: it writes nothing further (encode,
+ * nwords[b] = 0) or zeros for its remaining symbols (decode). */
+
+/* words that always hold a stream of nsymbols symbols: ceil(52 n / 32) + n / 2^19 + 3 */
+long long tmae_rans_stream_cap_words(long long nsymbols);
+
+/* stream b is written into the tail of slabs[b * cap_words, (b + 1) * cap_words): its words are the last
+ * nwords[b] of the slab.  The slab bound is checked before every store whatever cap_words is. */
+int tmae_rans_encode_streams(const int32_t* symbols, long long sym_seg_stride, long long sym_stream_stride,
+                             const int32_t* indexes, long long idx_seg_stride, long long idx_stream_stride,
+                             int nstreams, int nseg, int seg_len, const int32_t* cdfs, int cdf_stride,
+                             const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
+                             long long cap_words, int32_t* nwords, int32_t* status, void* stream);
+
+/* dense[word_offsets[b], word_offsets[b] + nwords[b]) = stream b; word_offsets[nstreams] = total words */
+int tmae_rans_pack_streams(const uint32_t* slabs, long long cap_words, const int32_t* nwords, int nstreams,
+                           uint32_t* dense, long long dense_cap_words, long long* word_offsets, int32_t* status,
+                           void* stream);
+
+/* decode segments [seg0, seg0 + nseg) of every stream from words[word_offsets[b], + word_counts[b]).  state /
+ * pos / status are per-stream device arrays that carry a stream from one call to the next; first != 0 starts
+ * the streams (state from the first two words, status cleared).  symbols = decoded value + offset. */
+int tmae_rans_decode_streams(const uint32_t* words, long long total_words, const long long* word_offsets,
+                             const int32_t* word_counts, const int32_t* indexes, long long idx_seg_stride,
+                             long long idx_stream_stride, int32_t* symbols, long long sym_seg_stride,
+                             long long sym_stream_stride, int nstreams, int seg0, int nseg, int seg_len,
+                             const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                             int ncdf, unsigned long long* state, int32_t* pos, int32_t* status, int first,
+                             void* stream);
+
 /* ---------------------------------------------------------------- Kodak eval harness (testing.py, §8f row 4)
  * HuffmanCoding (utils/huffman.py:6-171, host, no device work): the code table of a tensor of int64 values
  * (first-occurrence order, CPython heapq tie order, pre-order codes MSB-first in the low `lens` bits of

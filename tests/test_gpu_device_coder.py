@@ -1,0 +1,313 @@
+"""Per-image rANS streams coded on the GPU (csrc/rans_device.hip) and MCM.compress_batch / decompress_batch.
+
+Every comparison is an equality against the host coder (csrc/rans.cpp through textmae_amd.coder), which is the
+oracle here: the device kernels write, per stream, the bytes the host coder writes for that stream's symbols alone,
+and read them back to the same symbols.  Kernel tests use the real GaussianConditional tables (64 rows, 3 to ~3 k
+entries wide) and the EntropyBottleneck tables of the SMALL12 model.
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle import rans_oracle as ro
+from oracle.mcm_oracle import MCMConfig, make_state_dict
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+SMALL12 = dict(img_size=128, patch_size=16, encoder_embed_dim=128, encoder_depth=1, encoder_num_heads=2,
+               decoder_embed_dim=64, decoder_depth=1, decoder_num_heads=2, latent_depth=192, hyperprior_depth=96,
+               num_slices=12, num_keep_patches=16)
+
+
+def build(tmae, cfgd, seed, dtype=torch.float32):
+    cfg = MCMConfig(**cfgd)
+    m = tmae.MCM(**cfg.kwargs())
+    full = m.state_dict()
+    full.update(make_state_dict(cfg, seed))
+    m.load_state_dict(full)
+    m.compute_dtype = dtype
+    m = m.to(DEV).eval()
+    m.update(force=True)
+    return m
+
+
+def inputs(n, img, L, seed):
+    g = torch.Generator().manual_seed(seed)
+    imgs = (torch.rand(n, 3, img, img, generator=g) - 0.45) / 0.225
+    return imgs, torch.rand(n, L, generator=g)
+
+
+@pytest.fixture(scope="module")
+def gc(tmae):
+    from textmae_amd.entropy import GaussianConditional, get_scale_table
+
+    g = GaussianConditional(None).to(DEV)
+    g.update_scale_table(get_scale_table(), force=True)
+    sizes = g.host_tables()[1]
+    assert sizes.size == 64 and sizes.min() <= 8 and sizes.max() > 2048  # narrow and wide rows
+    return g
+
+
+@pytest.fixture(scope="module")
+def small(tmae):
+    return build(tmae, SMALL12, 11)
+
+
+def make_symbols(rng, idx, sizes, offsets, extremes=True, far_frac=0.05):
+    """~90 % inside the row's support, ~5 % 1..3 outside on either side, ~5 % (far_frac) |v| up to 2^20, two values
+    at +-2^27"""
+    maxv = sizes[idx].astype(np.int64) - 2  # values [0, maxv) are coded directly
+    off = offsets[idx].astype(np.int64)
+    v = off + (rng.random(idx.shape) * maxv).astype(np.int64)
+    u = rng.random(idx.shape)
+    k = rng.integers(1, 4, idx.shape)
+    side = rng.random(idx.shape) < 0.5
+    near = np.where(side, off - k, off + maxv - 1 + k)
+    far = rng.integers(-(1 << 20), (1 << 20) + 1, idx.shape)
+    v = np.where(u < 0.05, near, v)
+    v = np.where(u >= 1.0 - far_frac, far, v)
+    if extremes and v.size >= 8:
+        flat = v.reshape(-1)
+        flat[flat.size // 3] = 1 << 27
+        flat[2 * flat.size // 3] = -(1 << 27)
+    return v.astype(np.int32)
+
+
+class Case:
+    """nstreams x nseg x seg_len symbols / indexes in strided device buffers, and the host coder's strings"""
+
+    def __init__(self, model, nstreams, nseg, seg_len, seed, idx=None, pad=True, far_frac=0.05):
+        from textmae_amd.coder import RansEncoder
+
+        rng = np.random.default_rng(seed)
+        self.tabs_h = model.host_tables()
+        self.tabs = model.device_tables()
+        cdf, sizes, offsets = self.tabs_h
+        self.shape = (nstreams, nseg, seg_len)
+        shared = idx is not None  # one index array for all streams (stream stride 0), as the z channel indexes
+        self.idx_h = np.broadcast_to(idx, self.shape).copy() if shared else \
+            rng.integers(0, sizes.size, self.shape).astype(np.int32)
+        self.sym_h = make_symbols(rng, self.idx_h, sizes, offsets, far_frac=far_frac)
+        # symbols as the model lays them out, [segment][stream][seg_len]; indexes with strides of their own
+        self.sym_strides = (nstreams * seg_len, seg_len)
+        sym = np.ascontiguousarray(self.sym_h.transpose(1, 0, 2))
+        if shared:
+            self.idx_strides = (seg_len, 0)
+            ibuf = np.ascontiguousarray(self.idx_h[0])
+        else:
+            ts = seg_len + (9 if pad else 0)
+            ss = nstreams * ts + (7 if pad else 0)
+            self.idx_strides = (ss, ts)
+            ibuf = np.full(nseg * ss, -1, dtype=np.int32)
+            for j in range(nseg):
+                for b in range(nstreams):
+                    ibuf[j * ss + b * ts:j * ss + b * ts + seg_len] = self.idx_h[b, j]
+        self.sym = torch.from_numpy(sym.reshape(-1)).to(DEV)
+        self.idx = torch.from_numpy(ibuf.reshape(-1)).to(DEV)
+        self.want = [RansEncoder().encode_with_indexes(self.sym_h[b].reshape(-1), self.idx_h[b].reshape(-1),
+                                                       *self.tabs_h) for b in range(nstreams)]
+
+    def encode(self):
+        from textmae_amd.coder import DeviceRansEncoder
+
+        n, nseg, seg_len = self.shape
+        return DeviceRansEncoder().encode_streams(self.sym, self.sym_strides, self.idx, self.idx_strides, n, nseg,
+                                                  seg_len, self.tabs)
+
+    def decode(self, strings, calls, first_stream=0, nstreams=None):
+        """decode `calls` = [(seg0, nseg), ...] -> symbols [stream][segment][seg_len] (numpy), status"""
+        from textmae_amd.coder import DeviceRansDecoder
+
+        n, nseg, seg_len = self.shape
+        nstreams = n if nstreams is None else nstreams
+        dec = DeviceRansDecoder()
+        dec.set_streams(strings, DEV)
+        out = torch.full((nseg, n, seg_len), 7777, dtype=torch.int32, device=DEV)
+        for seg0, ns in calls:
+            dec.decode_streams(first_stream, nstreams, self.idx[first_stream * self.idx_strides[1]:], self.idx_strides,
+                               out.view(-1)[first_stream * self.sym_strides[1]:], self.sym_strides, seg0, ns, seg_len,
+                               self.tabs)
+        return out.cpu().numpy().transpose(1, 0, 2), dec.status()
+
+
+@pytest.fixture(scope="module")
+def case1(gc):
+    return Case(gc, 3, 3, 111, seed=1)
+
+
+def test_encode_streams_equal_host_coder(case1):
+    """test 1: 3 streams x 3 segments x 111 symbols, escapes up to 8 digits"""
+    sym, idx = case1.sym_h, case1.idx_h
+    cdf, sizes, offsets = case1.tabs_h
+    v = sym.astype(np.int64) - offsets[idx]
+    esc = (v < 0) | (v >= sizes[idx] - 2)
+    assert 0.05 < esc.mean() < 0.2 and np.abs(sym).max() == 1 << 27
+    got = case1.encode()
+    for b in range(3):
+        assert got[b] == case1.want[b], f"stream {b}"
+    tabs = [t.tolist() for t in case1.tabs_h]
+    assert got[0] == ro.encode(sym[0].reshape(-1).tolist(), idx[0].reshape(-1).tolist(), *tabs)
+
+
+@pytest.mark.parametrize("seg_len", [1, 63, 64, 65])
+def test_chunk_edges(gc, seg_len):
+    """test 2: symbol counts around the 64-symbol chunk"""
+    c = Case(gc, 2, 1, seg_len, seed=10 + seg_len)
+    assert c.encode() == c.want
+    got, status = c.decode(c.want, [(0, 1)])
+    assert not status.any() and np.array_equal(got, c.sym_h)
+
+
+def test_decode_streams(case1):
+    """test 3: one call, one call per segment with the state carried over, and stream 1 alone"""
+    got, status = case1.decode(case1.want, [(0, 3)])
+    assert not status.any() and np.array_equal(got, case1.sym_h)
+    got, status = case1.decode(case1.want, [(0, 1), (1, 1), (2, 1)])
+    assert not status.any() and np.array_equal(got, case1.sym_h)
+    got, status = case1.decode(case1.want, [(0, 3)], first_stream=1, nstreams=1)
+    assert not status.any() and np.array_equal(got[1], case1.sym_h[1])
+    assert (got[0] == 7777).all() and (got[2] == 7777).all()  # the other streams' outputs are untouched
+
+
+@pytest.mark.parametrize("hw", [1, 9])
+def test_entropy_bottleneck_tables(small, hw):
+    """test 4: 96 channel-indexed CDFs, the index array shared by the streams (index stream stride 0)"""
+    eb = small.entropy_bottleneck
+    zidx = eb._channel_indexes(hw)
+    c = Case(eb, 2, 1, 96 * hw, seed=20 + hw, idx=zidx)
+    want = [eb._code(c.sym_h[b].reshape(-1), zidx) for b in range(2)]
+    assert want == c.want
+    assert c.encode() == want
+    got, status = c.decode(want, [(0, 1)])
+    assert not status.any() and np.array_equal(got, c.sym_h)
+
+
+def test_decode_bounds(case1):
+    """test 5a: stream 1 loses its last 3 words but keeps its place in a buffer of the original size, so a reader
+    that ignored the length would see stale words, not unallocated memory: the status is set, the symbols up to the
+    missing words are right and zeros follow; the other streams decode as before"""
+    from textmae_amd import ops
+
+    n, nseg, seg_len = case1.shape
+    words = np.frombuffer(b"".join(case1.want), dtype=np.int32).copy()
+    lens = np.array([len(s) // 4 for s in case1.want], dtype=np.int32)
+    offs = np.concatenate([[0], np.cumsum(lens[:-1])]).astype(np.int64)
+    lens[1] -= 3
+    out = torch.full((nseg, n, seg_len), 7777, dtype=torch.int32, device=DEV)
+    state = torch.zeros(n, dtype=torch.int64, device=DEV)
+    pos = torch.zeros(n, dtype=torch.int32, device=DEV)
+    status = torch.zeros(n, dtype=torch.int32, device=DEV)
+    ops.rans_decode_streams(torch.from_numpy(words).to(DEV), words.size, torch.from_numpy(offs).to(DEV),
+                            torch.from_numpy(lens).to(DEV), case1.idx, case1.idx_strides, out, case1.sym_strides, n, 0,
+                            nseg, seg_len, case1.tabs, state, pos, status, True)
+    got, st = out.cpu().numpy().transpose(1, 0, 2), status.cpu().numpy()
+    assert st.tolist() == [0, 4, 0]
+    assert np.array_equal(got[0], case1.sym_h[0]) and np.array_equal(got[2], case1.sym_h[2])
+    g1, w1 = got[1].reshape(-1), case1.sym_h[1].reshape(-1)
+    stop = int(np.flatnonzero(g1 != w1)[0])
+    assert stop > g1.size // 2 and not g1[stop:].any()
+
+
+def test_encode_bounds(gc):
+    """test 5b: slabs of a quarter of the bound: every stream reports the overflow and nothing outside a slab is
+    written (guard words before and after every slab, streams launched one by one so each has its own guards).
+    A quarter of the bound is 13 bits per symbol, about what test 1's symbols cost, so this case has more far
+    escapes (a quarter of the symbols): the host coder's streams, asserted below, are well past the slab."""
+    from textmae_amd import ops
+
+    case1 = Case(gc, 3, 3, 111, seed=2, far_frac=0.25)
+    n, nseg, seg_len = case1.shape
+    cap = ops.rans_stream_cap_words(nseg * seg_len) // 4
+    assert all(len(s) // 4 > cap + cap // 4 for s in case1.want)
+    G, PAT = 16, 0x5A5A5A5A
+    buf = torch.full((n, G + cap + G), PAT, dtype=torch.int32, device=DEV)
+    nwords = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+    status = torch.zeros(n, dtype=torch.int32, device=DEV)
+    for b in range(n):
+        ops.rans_encode_streams(case1.sym[b * case1.sym_strides[1]:], case1.sym_strides,
+                                case1.idx[b * case1.idx_strides[1]:], case1.idx_strides, 1, nseg, seg_len, case1.tabs,
+                                buf[b, G:], cap, nwords[b:], status[b:])
+    buf_h = buf.cpu().numpy()
+    assert status.cpu().tolist() == [1] * n and nwords.cpu().tolist() == [0] * n
+    assert (buf_h[:, :G] == PAT).all() and (buf_h[:, G + cap:] == PAT).all()
+    # and all streams in one launch: contiguous slabs between two guards
+    buf = torch.full((G + n * cap + G,), PAT, dtype=torch.int32, device=DEV)
+    ops.rans_encode_streams(case1.sym, case1.sym_strides, case1.idx, case1.idx_strides, n, nseg, seg_len, case1.tabs,
+                            buf[G:], cap, nwords, status)
+    buf_h = buf.cpu().numpy()
+    assert status.cpu().tolist() == [1] * n
+    assert (buf_h[:G] == PAT).all() and (buf_h[G + n * cap:] == PAT).all()
+
+
+@pytest.fixture(scope="module")
+def small_batch(small):
+    imgs, scores = inputs(3, 128, 64, 5)
+    x, s = imgs.to(DEV), scores.to(DEV)
+    with torch.no_grad():
+        out = small.compress_batch(x, s)
+        streams = {k: np.array(v) for k, v in small._exec.last_streams.items()}
+    return x, s, out, streams
+
+
+def test_model_batch_strings_equal_host_coder(small, small_batch):
+    """test 6a: image b's y and z strings are the host coder's for that image's slice of last_streams"""
+    from textmae_amd.coder import RansEncoder
+
+    x, s, out, st = small_batch
+    B, S = 3, SMALL12["num_slices"]
+    gc, eb = small.gaussian_conditional, small.entropy_bottleneck
+    y_strings, z_strings = out["string"]
+    assert len(y_strings) == len(z_strings) == B and tuple(out["shape"]) == (1, 1)
+    ysym, yidx = st["y_symbols"].reshape(S, B, -1), st["y_indexes"].reshape(S, B, -1)
+    zidx = eb._channel_indexes(1)
+    for b in range(B):
+        want = RansEncoder().encode_with_indexes(ysym[:, b].reshape(-1), yidx[:, b].reshape(-1), *gc.host_tables())
+        assert y_strings[b] == want, f"y string of image {b}"
+        assert z_strings[b] == eb._code(st["z_symbols"][b].reshape(-1), zidx), f"z string of image {b}"
+
+
+def test_model_batch_round_trip(small, small_batch):
+    """test 6b: decompress_batch(compress_batch(x)) is the eval forward's x_hat and the host path's, bit for bit"""
+    x, s, out, _ = small_batch
+    with torch.no_grad():
+        rec = small.decompress_batch(out["string"], out["shape"], out["ids_restore"])["x_hat"]
+        fwd = small(x, s)["x_hat"]
+        host = small.compress(x, s)
+        host_rec = small.decompress(host["string"], host["shape"], host["ids_restore"])["x_hat"]
+    assert torch.equal(out["ids_restore"], host["ids_restore"])
+    assert torch.equal(rec, fwd)
+    assert torch.equal(rec, host_rec)
+
+
+def test_model_batch_corrupt_stream_names_image(small, small_batch):
+    x, s, out, _ = small_batch
+    y, z = [list(v) for v in out["string"]]
+    y[1] = y[1][:-12]
+    with pytest.raises(ValueError, match="y stream of image 1"):
+        small.decompress_batch([y, z], out["shape"], out["ids_restore"])
+    with pytest.raises(ValueError, match="one of each per image"):
+        small.decompress_batch([y[:2], z], out["shape"], out["ids_restore"])
+
+
+def test_batch_of_one_equals_compress(small, small_batch):
+    """test 7: at the reference's own batch size the two paths return the same strings"""
+    x, s, _, _ = small_batch
+    with torch.no_grad():
+        dev = small.compress_batch(x[:1], s[:1])
+        host = small.compress(x[:1], s[:1])
+    assert dev["string"] == host["string"]
+    assert tuple(dev["shape"]) == tuple(host["shape"]) and torch.equal(dev["ids_restore"], host["ids_restore"])
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_vitb_batch_round_trip(tmae, dtype):
+    """test 8: ViT-B 256^2, K = 144, batch 2: the round trip is the eval forward"""
+    m = build(tmae, dict(img_size=256, num_keep_patches=144), 3, dtype)
+    imgs, scores = inputs(2, 256, 256, 9)
+    with torch.no_grad():
+        fwd = m(imgs.to(DEV), scores.to(DEV))
+        out = m.compress_batch(imgs.to(DEV), scores.to(DEV))
+        rec = m.decompress_batch(out["string"], out["shape"], out["ids_restore"])
+    assert len(out["string"][0]) == len(out["string"][1]) == 2
+    assert torch.equal(rec["x_hat"], fwd["x_hat"])

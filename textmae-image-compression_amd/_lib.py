@@ -164,6 +164,10 @@ SIGNATURES = {
     "tmae_rans_decoder_create": [P, LL, ctypes.POINTER(ctypes.c_void_p)],
     "tmae_rans_decode_with_indexes": [P, P, LL, P, I, P, P, I, P],
     "tmae_rans_decoder_destroy": [P],
+    # per-image streams coded on the device (csrc/rans_device.hip)
+    "tmae_rans_encode_streams": [P, LL, LL, P, LL, LL, I, I, I, P, I, P, P, I, P, LL, P, P, P],
+    "tmae_rans_pack_streams": [P, LL, P, I, P, LL, P, P, P],
+    "tmae_rans_decode_streams": [P, LL, P, P, P, LL, LL, P, LL, LL, I, I, I, I, P, I, P, P, I, P, P, P, I, P],
     # Kodak eval harness: Huffman side info (host), metrics and the score-map producer (device)
     "tmae_huffman_build": [P, LL, P, P, P, I, ctypes.POINTER(I)],
     "tmae_huffman_encode": [P, LL, P, P, P, I, P, LL, ctypes.POINTER(LL)],
@@ -217,7 +221,8 @@ VALUE_FUNCS = {"tmae_wgrad_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_metrics_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_image_scores_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_qkv_attn_supported": ([I, I, I], ctypes.c_int),
-               "tmae_gemm_force_tile": ([I], ctypes.c_int)}
+               "tmae_gemm_force_tile": ([I], ctypes.c_int),
+               "tmae_rans_stream_cap_words": ([LL], ctypes.c_longlong)}
 
 _lib = None
 

@@ -1,0 +1,485 @@
+// Device rANS coder behind MCM.compress_batch / decompress_batch: one independent stream per image, each bit for
+// bit what the host coder (rans.cpp) writes for that image alone.  The format is restated from the top of rans.cpp:
+//   * 64-bit state in [2^31, 2^63), 32-bit words written from the END of the buffer and read from the front, an
+//     8-byte state flush (low word first) at the front of the stream;
+//   * 16-bit precision: symbol s of row c occupies [cdf[s], cdf[s+1]) of 2^16;
+//   * a value outside [offset, offset + size - 2) is coded as the row's last symbol (size - 2) followed by 4-bit
+//     bypass digits: the digit count (<= 8, so always one count digit), then the raw value (negatives 2|v|-1,
+//     overflow 2(v - max)) LSB digit first;
+//   * the encoder walks the symbols in reverse, last first, and for an escaped symbol puts the value digits (last
+//     first), the count digit and then the symbol, so the decoder reads symbol, count, digits in forward order.
+//
+// Stream layout (both directions): stream b codes segments j = 0..nseg-1 in order, segment j being seg_len
+// consecutive int32 at base + j * seg_stride + b * stream_stride (separate strides for symbols and indexes).
+//
+// One wave per stream: the only serial chain is the state update.  Per 64-symbol chunk the lanes do what is
+// parallel (index / symbol loads, clamp + escape, the cdf row reads and the exact reciprocal of the frequency for
+// encode) and keep the results in registers; the walk over the chunk is wave-uniform code that fetches symbol k's
+// fields with v_readlane, so the state lives in scalar registers and the chain is scalar arithmetic (lane 0
+// stores).  The chunks are software-pipelined, one stage per level of dependent loads, so that every load is
+// consumed one chunk walk after it was issued.  Every loop's trip count comes from the arguments, never from
+// stream content.
+#include "common.h"
+
+namespace {
+
+constexpr uint64_t kRansLow = 1ull << 31;
+constexpr int kWave = 64;
+constexpr int kMaxWinRows = 128;  // 64-entry int32 windows kept in LDS: 32 KB at most
+
+// per-stream status words (0 = fine)
+enum {
+  kStOverflow = 1,  // encode / pack: the output slab (or dense buffer) would overflow
+  kStSymbol = 2,    // decode: symbol search fell outside the row
+  kStEscape = 3,    // decode: escape longer than 8 digits
+  kStOverrun = 4,   // decode: read past the stream's length
+  kStIndex = 5,     // a table index outside [0, ncdf)
+  kStStream = 6,    // decode: stream offset / length / position outside the word buffer
+};
+
+// lane `lane` (wave-uniform) of v, as a scalar
+__device__ __forceinline__ int bcast_i(int v, int lane) {
+  return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane));
+}
+__device__ __forceinline__ uint32_t bcast_u(uint32_t v, int lane) { return (uint32_t)bcast_i((int)v, lane); }
+
+// ------------------------------------------------------------------------------------------------ encode
+struct EncState {
+  uint64_t x;
+  long long head;  // words [head, cap) of the slab are written
+  int st;
+};
+
+__device__ __forceinline__ void enc_emit(EncState& e, uint32_t* __restrict__ slab, int lane) {
+  if (e.head <= 0) {  // the slab is full: stop this stream, never write outside it
+    e.st = kStOverflow;
+    return;
+  }
+  --e.head;
+  if (lane == 0) slab[e.head] = (uint32_t)e.x;
+  e.x >>= 32;
+}
+
+// raw bits: freq = 2^12 of 2^16, so x_max = 2^12 << 47
+__device__ __forceinline__ void enc_put_bits(EncState& e, uint32_t* __restrict__ slab, int lane, uint32_t val) {
+  if (e.st) return;
+  if (e.x >= (1ull << 59)) enc_emit(e, slab, lane);
+  if (e.st) return;
+  e.x = (e.x << 4) | val;
+}
+
+// exact reciprocal of freq in [2, 2^16) (ryg_rans Rans64EncSymbolInit): floor(x / freq) = mulhi(x, rcp) >> shift for
+// x < 2^63, rcp = ceil(2^(shift + 64) / freq), shift = ceil(log2 freq) - 1; the 128-bit dividend has the base-2^16
+// digits [2^(shift+15), 0, 0, freq - 1], so the long division is four 32-bit divisions
+__device__ __forceinline__ uint64_t enc_reciprocal(uint32_t freq, uint32_t& shift) {
+  const uint32_t bits = 32u - (uint32_t)__clz((int)(freq - 1));  // ceil(log2 freq)
+  const uint32_t a = 1u << (bits + 15);
+  const uint32_t q1 = a / freq, r1 = a - q1 * freq;
+  const uint32_t q2 = (r1 << 16) / freq, r2 = (r1 << 16) - q2 * freq;
+  const uint32_t q3 = (r2 << 16) / freq, r3 = (r2 << 16) - q3 * freq;
+  const uint32_t q4 = ((r3 << 16) + (freq - 1)) / freq;
+  shift = bits - 1;
+  return ((((uint64_t)q1 << 16) + q2) << 32) + (((uint64_t)q3 << 16) + q4);
+}
+
+__global__ void __launch_bounds__(kWave)
+rans_encode_streams_kernel(const int* __restrict__ sym, long long sym_ss, long long sym_ts, const int* __restrict__ idx,
+                           long long idx_ss, long long idx_ts, int nseg, int seg_len, const int* __restrict__ cdfs,
+                           int cdf_stride, const int* __restrict__ sizes, const int* __restrict__ offs, int ncdf,
+                           uint32_t* __restrict__ slabs, long long cap, int* __restrict__ nwords,
+                           int* __restrict__ status) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = nseg * seg_len;
+  uint32_t* __restrict__ slab = slabs + (size_t)b * cap;
+  EncState e{kRansLow, cap, 0};
+  const int nchunks = (n + kWave - 1) / kWave;
+  // pipeline registers.  Stage A: index and symbol of a chunk; B: its row's size and offset; C: clamp / escape and
+  // the two cdf entries; D: reciprocal, then the walk.  In iteration t the stages hold chunks t, t-1, t-2, t-3 of the
+  // reversed order (chunk nchunks-1 first).
+  int a_ci = 0, a_v = 0;
+  int b_ci = 0, b_v = 0, b_size = 3, b_off = 0;
+  uint32_t c_start = 0, c_next = 1, c_raw = 0, c_flags = 0;  // flags: escaped | ndig << 1 | bad index << 8
+  bool b_bad = false;
+  for (int t = 0; t < nchunks + 3 && e.st == 0; ++t) {
+    // ---- D: fields of the chunk walked in this iteration, from the cdf entries loaded one iteration ago
+    const int cd = nchunks - 1 - (t - 3);
+    uint32_t d_rcp_lo = 0, d_rcp_hi = 0, d_bias = 0, d_meta = 0, d_raw = c_raw;
+    bool d_bad = false;
+    if (t >= 3) {
+      const uint32_t freq = c_next - c_start;
+      uint32_t shift = 0;
+      uint64_t rcp = ~0ull;
+      d_bias = c_start + (1u << 16) - 1;  // freq 1: q = x - 1, so x + bias + q (2^16 - 1) = (x << 16) + start
+      if (freq >= 2) {
+        rcp = enc_reciprocal(freq, shift);
+        d_bias = c_start;
+      }
+      d_rcp_lo = (uint32_t)rcp;
+      d_rcp_hi = (uint32_t)(rcp >> 32);
+      // meta = freq (17 bits) | shift << 17 (5 bits) | escaped << 22 | ndig << 23
+      d_meta = freq | (shift << 17) | ((c_flags & 1u) << 22) | (((c_flags >> 1) & 15u) << 23);
+      d_bad = (c_flags >> 8) & 1u;
+    }
+    // ---- C: clamp and escape the value, issue the loads of cdf[value] and cdf[value + 1]
+    if (t >= 2 && t < nchunks + 2) {
+      const int max_value = b_size - 2;
+      int value = (int)((uint32_t)b_v - (uint32_t)b_off);
+      uint32_t raw = 0, esc = 0, ndig = 0;
+      if (value < 0) {
+        raw = (uint32_t)(-2 * (long long)value - 1);
+        value = max_value;
+      } else if (value >= max_value) {
+        raw = (uint32_t)(2 * (long long)(value - max_value));
+        value = max_value;
+      }
+      if (value == max_value) {
+        esc = 1;
+#pragma unroll
+        for (int d = 0; d < 8; ++d) ndig += (raw >> (4 * d)) != 0 ? 1 : 0;  // nibbles up to the top non-zero one
+      }
+      const int* __restrict__ row = cdfs + (size_t)b_ci * cdf_stride;
+      c_start = (uint32_t)row[value];
+      c_next = (uint32_t)row[value + 1];
+      c_raw = raw;
+      c_flags = esc | (ndig << 1) | (b_bad ? 1u << 8 : 0u);
+    }
+    // ---- B: the row's size and offset (lanes past the end of the stream code nothing: row 0, never walked)
+    if (t >= 1 && t < nchunks + 1) {
+      b_bad = a_ci < 0 || a_ci >= ncdf;
+      b_ci = b_bad ? 0 : a_ci;
+      b_v = a_v;
+      b_size = sizes[b_ci];
+      b_off = offs[b_ci];
+    }
+    // ---- A: index and symbol
+    if (t < nchunks) {
+      const int i = (nchunks - 1 - t) * kWave + lane;
+      a_ci = 0;
+      a_v = 0;
+      if (i < n) {
+        const int j = i / seg_len, k = i - j * seg_len;
+        a_ci = idx[j * idx_ss + b * idx_ts + k];
+        a_v = sym[j * sym_ss + b * sym_ts + k];
+      }
+    }
+    if (t < 3) continue;
+    // ---- walk chunk cd, last symbol first
+    if (__any(d_bad)) {
+      e.st = kStIndex;
+      break;
+    }
+    const int cnt = min(kWave, n - cd * kWave);
+    for (int k = cnt - 1; k >= 0 && e.st == 0; --k) {
+      const uint32_t m = bcast_u(d_meta, k);
+      const uint32_t freq = m & 0x1FFFF, shift = (m >> 17) & 31;
+      if ((m >> 22) & 1) {
+        const uint32_t r = bcast_u(d_raw, k);
+        const int ndig = (int)(m >> 23);
+        for (int d = 7; d >= 0; --d)
+          if (d < ndig) enc_put_bits(e, slab, lane, (r >> (4 * d)) & 15u);
+        enc_put_bits(e, slab, lane, (uint32_t)ndig);
+        if (e.st) break;
+      }
+      if ((uint32_t)(e.x >> 32) >= (freq << 15)) {  // x >= freq << 47
+        enc_emit(e, slab, lane);
+        if (e.st) break;
+      }
+      const uint64_t rcp = (uint64_t)bcast_u(d_rcp_lo, k) | ((uint64_t)bcast_u(d_rcp_hi, k) << 32);
+      const uint64_t q = __umul64hi(e.x, rcp) >> shift;
+      e.x = e.x + bcast_u(d_bias, k) + q * (uint64_t)((1u << 16) - freq);
+    }
+  }
+  // 8-byte state flush: high word first (the buffer grows downward), so the stream starts with the low word
+  if (e.st == 0 && e.head < 2) e.st = kStOverflow;
+  if (e.st == 0) {
+    e.head -= 2;
+    if (lane == 0) {
+      slab[e.head + 1] = (uint32_t)(e.x >> 32);
+      slab[e.head] = (uint32_t)e.x;
+    }
+  }
+  if (lane == 0) {
+    nwords[b] = e.st ? 0 : (int)(cap - e.head);
+    status[b] = e.st;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ pack
+// dense[offsets[b] .. offsets[b] + nwords[b]) = the tail of slab b; offsets[nstreams] = the total
+__global__ void __launch_bounds__(256)
+rans_pack_streams_kernel(const uint32_t* __restrict__ slabs, long long cap, const int* __restrict__ nwords, int nstreams,
+                         uint32_t* __restrict__ dense, long long dense_cap, long long* __restrict__ offsets,
+                         int* __restrict__ status) {
+  __shared__ long long s_part[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  long long part = 0;
+  for (int i = t; i < b; i += 256) part += min((long long)max(nwords[i], 0), cap);
+  s_part[t] = part;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) s_part[t] += s_part[t + s];
+    __syncthreads();
+  }
+  const long long off = s_part[0];
+  long long nw = min((long long)max(nwords[b], 0), cap);
+  if (off + nw > dense_cap) {
+    nw = 0;
+    if (t == 0) status[b] = kStOverflow;
+  }
+  if (t == 0) {
+    offsets[b] = off;
+    if (b == nstreams - 1) offsets[nstreams] = off + nw;
+  }
+  const uint32_t* __restrict__ src = slabs + (size_t)b * cap + (cap - nw);
+  for (long long i = t; i < nw; i += 256) dense[off + i] = src[i];
+}
+
+// ------------------------------------------------------------------------------------------------ decode
+__device__ __forceinline__ int win_start(int size) { return size > kWave ? size / 2 - kWave / 2 : 0; }
+
+struct DecState {
+  uint64_t x;
+  int pos, len;    // next word to read, words in the stream
+  int wbase;       // lane l of wbuf holds word wbase + l
+  uint32_t wbuf;
+  int st;
+};
+
+__device__ __forceinline__ uint32_t dec_next_word(DecState& d, const uint32_t* __restrict__ w, int lane) {
+  if (d.pos < 0 || d.pos >= d.len) {
+    d.st = kStOverrun;
+    return 0;
+  }
+  int r = d.pos - d.wbase;
+  if (r < 0 || r >= kWave) {
+    d.wbase = d.pos;
+    d.wbuf = d.pos + lane < d.len ? w[d.pos + lane] : 0u;
+    r = 0;
+  }
+  ++d.pos;
+  return bcast_u(d.wbuf, r);
+}
+
+__device__ __forceinline__ uint32_t dec_get_bits4(DecState& d, const uint32_t* __restrict__ w, int lane) {
+  const uint32_t v = (uint32_t)(d.x & 15u);
+  d.x >>= 4;
+  if (d.x < kRansLow) d.x = (d.x << 32) | dec_next_word(d, w, lane);
+  return v;
+}
+
+__global__ void __launch_bounds__(kWave)
+rans_decode_streams_kernel(const uint32_t* __restrict__ words, long long total_words, const long long* __restrict__ woff,
+                           const int* __restrict__ wlen, const int* __restrict__ idx, long long idx_ss, long long idx_ts,
+                           int* __restrict__ out, long long out_ss, long long out_ts, int seg0, int nseg, int seg_len,
+                           const int* __restrict__ cdfs, int cdf_stride, const int* __restrict__ sizes,
+                           const int* __restrict__ offs, int ncdf, int win_rows, unsigned long long* __restrict__ state,
+                           int* __restrict__ pos, int* __restrict__ status, int first) {
+  extern __shared__ int s_win[];  // [win_rows][64]: entries win_start(size) + l of each row, INT_MAX past its end
+  const int b = blockIdx.x, lane = threadIdx.x;
+#pragma unroll 4
+  for (int r = 0; r < win_rows; ++r) {
+    const int size = sizes[r], ent = win_start(size) + lane;
+    s_win[r * kWave + lane] = ent < size ? cdfs[(size_t)r * cdf_stride + ent] : INT_MAX;
+  }
+  __syncthreads();
+
+  DecState d{0, 0, 0, 0, 0u, first ? 0 : status[b]};
+  const long long off = woff[b];
+  d.len = wlen[b];
+  if (d.st == 0 && (off < 0 || d.len < 2 || off + d.len > total_words)) d.st = kStStream;
+  const uint32_t* __restrict__ w = words + (d.st == 0 ? off : 0);  // read only while st == 0
+  if (d.st == 0) {
+    if (first) {
+      d.x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+      d.pos = 2;
+    } else {
+      d.x = state[b];
+      d.pos = pos[b];
+      if (d.pos < 2 || d.pos > d.len) d.st = kStStream;
+    }
+  }
+  if (d.st == 0) {
+    d.wbase = d.pos;
+    d.wbuf = d.pos + lane < d.len ? w[d.pos + lane] : 0u;
+  }
+
+  const int n = nseg * seg_len;
+  const int nchunks = (n + kWave - 1) / kWave;
+  // pipeline registers.  Stage A: the indexes of a chunk; B: their rows' sizes and offsets; then the walk.  In
+  // iteration t the stages hold chunks t, t-1 and t-2.
+  int a_ci = 0;
+  int b_ci = 0, b_size = 3, b_off = 0;
+  bool b_bad = false;
+  for (int t = 0; t < nchunks + 2; ++t) {
+    const int ci = b_ci, size_l = b_size, off_l = b_off;
+    const bool bad = b_bad;
+    if (t >= 1 && t < nchunks + 1) {
+      b_bad = a_ci < 0 || a_ci >= ncdf;
+      b_ci = b_bad ? 0 : a_ci;
+      b_size = sizes[b_ci];
+      b_off = offs[b_ci];
+    }
+    if (t < nchunks) {
+      const int i = t * kWave + lane;
+      a_ci = 0;
+      if (i < n) {
+        const int j = i / seg_len, kk = i - j * seg_len;
+        a_ci = idx[(seg0 + j) * idx_ss + b * idx_ts + kk];
+      }
+    }
+    if (t < 2) continue;
+    // ---- walk chunk c
+    const int c = t - 2;
+    if (d.st == 0 && __any(bad)) d.st = kStIndex;
+    int myval = 0;
+    const int cnt = min(kWave, n - c * kWave);
+    // the probe window of symbol k + 1 is read while symbol k is decoded (its address does not depend on the state);
+    // a row without a window reads as INT_MAX: no entry <= cum, so the search over the whole row runs
+    int ck_n = bcast_i(ci, 0);
+    int wv_n = ck_n < win_rows ? s_win[ck_n * kWave + lane] : INT_MAX;
+    for (int k = 0; k < cnt && d.st == 0; ++k) {
+      const int ck = ck_n, wv = wv_n;
+      const int size = bcast_i(size_l, k);
+      if (k + 1 < cnt) {
+        ck_n = bcast_i(ci, k + 1);
+        wv_n = ck_n < win_rows ? s_win[ck_n * kWave + lane] : INT_MAX;
+      }
+      const int cum = (int)(d.x & 0xFFFFu);
+      const int* __restrict__ row = cdfs + (size_t)ck * cdf_stride;
+      int s = -1, start = 0, next = 0;
+      const int cw = __popcll(__ballot(wv <= cum));  // wave-wide probe of the row's centre window
+      if (cw >= 1 && cw < kWave) {
+        s = win_start(size) + cw - 1;
+        start = bcast_i(wv, cw - 1);
+        next = bcast_i(wv, cw);
+      } else {  // 64-way search over the whole row: s = last entry <= cum
+        int lo = 0, len_r = size;
+        bool ok = true;
+        for (int lvl = 0; lvl < 6 && len_r > kWave && ok; ++lvl) {
+          const int step = (len_r + kWave - 1) / kWave;
+          const long long ent = (long long)lane * step;
+          const int v = ent < len_r ? row[lo + ent] : INT_MAX;
+          const int c1 = __popcll(__ballot(v <= cum));
+          if (c1 == 0) {
+            ok = false;
+          } else {
+            lo += (c1 - 1) * step;
+            len_r = min(step, len_r - (c1 - 1) * step);
+          }
+        }
+        if (ok && len_r <= kWave) {
+          const int v = lane < len_r ? row[lo + lane] : INT_MAX;
+          s = lo + __popcll(__ballot(v <= cum)) - 1;
+        }
+        if (s >= 0 && s <= size - 2) {
+          start = row[s];
+          next = row[s + 1];
+        }
+      }
+      if (s < 0 || s > size - 2) {
+        d.st = kStSymbol;
+        break;
+      }
+      // advance: x = freq * (x >> 16) + (x & 0xFFFF) - start, then renormalise
+      d.x = (uint64_t)(uint32_t)(next - start) * (d.x >> 16) + (uint64_t)(uint32_t)cum - (uint32_t)start;
+      if (d.x < kRansLow) d.x = (d.x << 32) | dec_next_word(d, w, lane);
+      int value = s;
+      const int max_value = size - 2;
+      if (s == max_value && d.st == 0) {
+        const uint32_t ndig = dec_get_bits4(d, w, lane);  // 15 = "another count digit follows": more than 8 anyway
+        if (ndig > 8) {
+          d.st = kStEscape;
+          break;
+        }
+        uint32_t raw = 0;
+        for (uint32_t q = 0; q < 8; ++q)
+          if (q < ndig && d.st == 0) raw |= dec_get_bits4(d, w, lane) << (4 * q);
+        const int half = (int)(raw >> 1);
+        value = (raw & 1) ? -half - 1 : half + max_value;
+      }
+      if (d.st) break;
+      if (lane == k) myval = (int)((uint32_t)value + (uint32_t)off_l);
+    }
+    const int i = c * kWave + lane;
+    if (i < n) {  // zeros from the failing symbol on
+      const int j = i / seg_len, kk = i - j * seg_len;
+      out[(seg0 + j) * out_ss + b * out_ts + kk] = myval;
+    }
+  }
+  if (lane == 0) {
+    state[b] = d.x;
+    pos[b] = d.pos;
+    status[b] = d.st;
+  }
+}
+
+}  // namespace
+
+// words that always hold a stream of n symbols.  With the state at or above 2^31 (2^27 for a bypass digit, after a
+// word store) a put multiplies it by at most 2^16 (1 + 2^-15) (symbol) or 2^4 (1 + 2^-27) (bypass digit), a word
+// store divides it by at least 2^32, and it starts at 2^31 and ends at or above 2^31: 32 W <= n (16 + 9 * 4 + 4.5e-5)
+// bits.  The excess over 52 n / 32 is below n / 2^19 words; + 2 words of state flush, + 1 spare.
+extern "C" long long tmae_rans_stream_cap_words(long long nsymbols) {
+  if (nsymbols < 0) return -1;
+  return (52 * nsymbols + 31) / 32 + (nsymbols >> 19) + 3;
+}
+
+#define RANSD_TABLES(name)                                                                             \
+  TMAE_REQUIRE(cdfs && cdf_sizes && offsets && ncdf > 0 && cdf_stride > 1, name ": CDF tables required")
+
+#define RANSD_SHAPE(name)                                                                                          \
+  TMAE_REQUIRE(nstreams > 0, name ": nstreams = %d must be positive", nstreams);                                   \
+  TMAE_REQUIRE(nseg > 0 && seg_len > 0 && (long long)nseg * seg_len <= (1ll << 30),                                \
+               name ": nseg * seg_len = %d * %d must be in [1, 2^30]", nseg, seg_len)
+
+extern "C" int tmae_rans_encode_streams(const int32_t* symbols, long long sym_seg_stride, long long sym_stream_stride,
+                                        const int32_t* indexes, long long idx_seg_stride, long long idx_stream_stride,
+                                        int nstreams, int nseg, int seg_len, const int32_t* cdfs, int cdf_stride,
+                                        const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
+                                        long long cap_words, int32_t* nwords, int32_t* status, void* stream) {
+  TMAE_REQUIRE(symbols && indexes && slabs && nwords && status, "tmae_rans_encode_streams: NULL buffer");
+  RANSD_SHAPE("tmae_rans_encode_streams");
+  RANSD_TABLES("tmae_rans_encode_streams");
+  TMAE_REQUIRE(cap_words > 0 && cap_words <= INT32_MAX, "tmae_rans_encode_streams: cap_words = %lld outside [1, 2^31)",
+               cap_words);
+  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
+               "tmae_rans_encode_streams: negative stride");
+  hipLaunchKernelGGL(rans_encode_streams_kernel, dim3(nstreams), dim3(kWave), 0, (hipStream_t)stream, symbols,
+                     sym_seg_stride, sym_stream_stride, indexes, idx_seg_stride, idx_stream_stride, nseg, seg_len, cdfs,
+                     cdf_stride, cdf_sizes, offsets, ncdf, slabs, cap_words, nwords, status);
+  TMAE_LAUNCH_CHECK("tmae_rans_encode_streams");
+}
+
+extern "C" int tmae_rans_pack_streams(const uint32_t* slabs, long long cap_words, const int32_t* nwords, int nstreams,
+                                      uint32_t* dense, long long dense_cap_words, long long* word_offsets,
+                                      int32_t* status, void* stream) {
+  TMAE_REQUIRE(slabs && nwords && dense && word_offsets && status, "tmae_rans_pack_streams: NULL buffer");
+  TMAE_REQUIRE(nstreams > 0, "tmae_rans_pack_streams: nstreams = %d must be positive", nstreams);
+  TMAE_REQUIRE(cap_words > 0 && dense_cap_words > 0, "tmae_rans_pack_streams: capacities must be positive");
+  hipLaunchKernelGGL(rans_pack_streams_kernel, dim3(nstreams), dim3(256), 0, (hipStream_t)stream, slabs, cap_words,
+                     nwords, nstreams, dense, dense_cap_words, word_offsets, status);
+  TMAE_LAUNCH_CHECK("tmae_rans_pack_streams");
+}
+
+extern "C" int tmae_rans_decode_streams(const uint32_t* words, long long total_words, const long long* word_offsets,
+                                        const int32_t* word_counts, const int32_t* indexes, long long idx_seg_stride,
+                                        long long idx_stream_stride, int32_t* symbols, long long sym_seg_stride,
+                                        long long sym_stream_stride, int nstreams, int seg0, int nseg, int seg_len,
+                                        const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                        const int32_t* offsets, int ncdf, unsigned long long* state, int32_t* pos,
+                                        int32_t* status, int first, void* stream) {
+  TMAE_REQUIRE(words && word_offsets && word_counts && indexes && symbols && state && pos && status,
+               "tmae_rans_decode_streams: NULL buffer");
+  RANSD_SHAPE("tmae_rans_decode_streams");
+  RANSD_TABLES("tmae_rans_decode_streams");
+  TMAE_REQUIRE(total_words > 0 && seg0 >= 0, "tmae_rans_decode_streams: total_words = %lld, seg0 = %d", total_words,
+               seg0);
+  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
+               "tmae_rans_decode_streams: negative stride");
+  const int win_rows = ncdf < kMaxWinRows ? ncdf : kMaxWinRows;
+  hipLaunchKernelGGL(rans_decode_streams_kernel, dim3(nstreams), dim3(kWave), (size_t)win_rows * kWave * sizeof(int),
+                     (hipStream_t)stream, words, total_words, word_offsets, word_counts, indexes, idx_seg_stride,
+                     idx_stream_stride, symbols, sym_seg_stride, sym_stream_stride, seg0, nseg, seg_len, cdfs,
+                     cdf_stride, cdf_sizes, offsets, ncdf, win_rows, state, pos, status, first ? 1 : 0);
+  TMAE_LAUNCH_CHECK("tmae_rans_decode_streams");
+}

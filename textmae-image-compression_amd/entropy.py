@@ -82,6 +82,21 @@ class EntropyModel(nn.Module):
             self._host_tables_cache = cache
         return cache[1]
 
+    def device_tables(self, device=None):
+        """host_tables() as int32 device tensors for the device coder (ops.rans_*_streams), cached like them.
+        The tables are validated here, once, where they are built: the kernels trust them."""
+        tabs = self.host_tables()
+        device = torch.device(device) if device is not None else self._quantized_cdf.device
+        cache = getattr(self, "_device_tables_cache", None)
+        if cache is None or cache[0] is not tabs or cache[1] != device:
+            from .coder import BufferedRansEncoder
+
+            empty = np.empty(0, dtype=np.int32)
+            BufferedRansEncoder().encode_with_indexes(empty, empty, *tabs)  # the host coder's table check
+            cache = (tabs, device, tuple(torch.from_numpy(t).to(device) for t in tabs))
+            self._device_tables_cache = cache
+        return cache[2]
+
     @staticmethod
     def quantize_symbols(inputs, means=None):
         """quantize(inputs, "symbols", means): round(inputs - means).int() (module-level convenience)"""

@@ -17,6 +17,7 @@ operand type: torch.float32 (exact f32 MFMA; the parity path, default) or torch.
 """
 from __future__ import annotations
 
+import collections.abc
 import os
 
 from functools import partial
@@ -352,6 +353,56 @@ class MCM(CompressionModel):
             ex = self._executor(len(strings[1]), dev)
             return {"x_hat": ex.decompress(strings, shape, ids_restore)}
 
+    def compress_batch(self, imgs, total_scores):
+        """compress with one independent record per image, coded on the device (csrc/rans_device.hip) ->
+        {"string": [y_strings, z_strings], "shape", "ids_restore"}, len(y_strings) == len(z_strings) == B.
+        Image b's (y_strings[b], z_strings[b]) are the strings MCM.compress (MCM.py:805-894) returns for that image
+        alone.  Same preconditions as compress."""
+        if not imgs.is_cuda:
+            raise ValueError("MCM.compress_batch runs on the MI355X kernels: move the model and inputs to the GPU")
+        self.entropy_bottleneck._check_cdf()
+        self.gaussian_conditional._check_cdf()
+        with torch.no_grad():
+            ex = self._executor(imgs.shape[0], imgs.device)
+            return ex.compress_batch(imgs, total_scores)
+
+    def decompress_batch(self, strings, shape, ids_restore=None):
+        """inverse of compress_batch -> {"x_hat"}: strings = [y_strings, z_strings], one of each per image.  The
+        streams are decoded on the device inside the slice loop; a corrupt stream raises ValueError naming its image
+        after the whole batch has been enqueued."""
+        assert isinstance(strings, list) and len(strings) == 2
+        if ids_restore is None:
+            raise ValueError("MCM.decompress_batch needs ids_restore (the decoder unshuffles by it, MCM.py:667-669)")
+        if len(strings[0]) != len(strings[1]):
+            raise ValueError(f"{len(strings[0])} y strings but {len(strings[1])} z strings: one of each per image")
+        self.entropy_bottleneck._check_cdf()
+        self.gaussian_conditional._check_cdf()
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise ValueError("MCM.decompress_batch runs on the MI355X kernels: move the model to the GPU")
+        with torch.no_grad():
+            ex = self._executor(len(strings[1]), dev)
+            return {"x_hat": ex.decompress_batch(strings, shape, ids_restore)}
+
+
+class _LazyStreams(collections.abc.Mapping):
+    """_Executor.last_streams of compress_batch: the keys compress sets, as host arrays copied from the device on
+    first use (the batch path itself never copies the symbols to the host)"""
+
+    def __init__(self, **tensors):
+        self._t, self._h = tensors, {}
+
+    def __getitem__(self, key):
+        if key not in self._h:
+            self._h[key] = self._t[key].cpu().numpy()
+        return self._h[key]
+
+    def __iter__(self):
+        return iter(self._t)
+
+    def __len__(self):
+        return len(self._t)
+
 
 def _interleave(layers):
     out = []
@@ -663,6 +714,83 @@ class _Executor:
         self._slices(self._gc_decompress(decoder))
         shuf = ops.invert_permutation(ids_restore.to(self.device))
         return self._back(shuf, m.encoder_embed.proj.in_channels)
+
+    def compress_batch(self, imgs, scores):
+        """compress with the device coder: the same symbol / index buffers, coded as one y and one z stream per
+        image (image b's y stream = its [slice][channel][pixel] symbols), the reference's batch-1 format B times"""
+        from .coder import DeviceRansEncoder
+
+        m, B = self.m, self.batch
+        N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
+        eb, gc = m.entropy_bottleneck, m.gaussian_conditional
+        imgs = self._check_imgs(imgs)
+        shuf, rest = self._front(imgs, scores)
+        ops.eb_likelihood(eb, self.Z, B, N, hz * hz, lik=self.ZLIK, zhat=self.ZHAT, table=self.eb_table)
+        zsym = ops.eb_symbols(eb, self.Z, B, N, hz * hz, table=self.eb_table)
+        self._h_s()
+        sym = torch.empty(S * B * sw * HW, dtype=torch.int32, device=self.device)
+        idx = torch.empty_like(sym)
+        self._slices(self._gc_compress(sym, idx))
+        enc = self.__dict__.get("_dev_encoder")
+        if enc is None:
+            enc = self._dev_encoder = DeviceRansEncoder()
+        zidx = self._z_indexes()
+        nz = N * hz * hz
+        z_strings = enc.encode_streams(zsym, (0, nz), zidx, (0, 0), B, 1, nz, eb.device_tables(),
+                                       what="z stream of image")
+        y_strings = enc.encode_streams(sym, (B * sw * HW, sw * HW), idx, (B * sw * HW, sw * HW), B, S, sw * HW,
+                                       gc.device_tables(), what="y stream of image")
+        self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # rate diagnostics
+        return {"string": [y_strings, z_strings], "shape": torch.Size([hz, hz]), "ids_restore": rest}
+
+    def _z_indexes(self):
+        """EntropyBottleneck channel indexes of one image's z symbols [C][hz*hz] on the device (shared by all images)"""
+        zidx = self.__dict__.get("_zidx")
+        if zidx is None:
+            zidx = self.m.entropy_bottleneck._channel_indexes(self.hz * self.hz)
+            zidx = self._zidx = torch.from_numpy(zidx).to(self.device)
+        return zidx
+
+    def decompress_batch(self, strings, shape, ids_restore):
+        """decompress of per-image records: every string goes up in one copy, the z and y streams are decoded by
+        device kernels (the y streams inside the slice loop, one call per slice step), and nothing synchronises with
+        the host until the status words are read after the last kernel of _back has been enqueued"""
+        from .coder import DeviceRansDecoder, _raise_status
+
+        m, B = self.m, self.batch
+        N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
+        eb, gc = m.entropy_bottleneck, m.gaussian_conditional
+        if tuple(int(v) for v in shape) != (hz, hz):
+            raise ValueError(f"shape {tuple(shape)} does not match this model's z grid ({hz}, {hz})")
+        # everything that touches the host comes first: tables, the scale bound, ids, then the one upload
+        etabs, gtabs = eb.device_tables(), gc.device_tables()
+        bound = float(gc.scale_bound) if gc.scale_bound is not None else 0.11
+        zidx = self._z_indexes()
+        rest = ids_restore.to(self.device)
+        dec = DeviceRansDecoder()
+        dec.set_streams(list(strings[0]) + list(strings[1]), self.device)  # streams [0, B): y, [B, 2B): z
+        nz, per = N * hz * hz, B * sw * HW
+        zsym = torch.empty((B, N, hz * hz), dtype=torch.int32, device=self.device)
+        dec.decode_streams(B, B, zidx, (0, 0), zsym, (0, nz), 0, 1, nz, etabs)
+        ops.eb_dequantize(eb, zsym, B, N, hz * hz, self.ZHAT, table=self.eb_table)
+        self._h_s()
+        idx = torch.empty(S * per, dtype=torch.int32, device=self.device)
+        sym = torch.empty_like(idx)
+        M, dt = m.latent_depth, self.dtype
+
+        def step(i0, nbs, mu, sigma, ms_stride):
+            ops.gc_indexes(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:])
+            dec.decode_streams(0, B, idx, (per, sw * HW), sym, (per, sw * HW), i0, nbs, sw * HW, gtabs)
+            ops.gc_dequantize(sym[i0 * per:], mu, ms_stride, sw, B, HW, nbs, sw, i0 * sw, self.SUPY, dt, M, self.YPRE,
+                              M)
+
+        self._slices(step)
+        shuf = ops.invert_permutation(rest)
+        x_hat = self._back(shuf, m.encoder_embed.proj.in_channels)
+        status = dec.status()  # the only synchronisation: after everything is enqueued
+        _raise_status(status[:B], "y stream of image")
+        _raise_status(status[B:], "z stream of image")
+        return x_hat
 
     def encode(self, imgs, scores):
         """the encoder stage alone (MCM.forward_encoder): -> (x_remain f32 [B, K, E], ids_restore), both fresh;

@@ -20,6 +20,7 @@ __all__ = [
     "mask_rows", "decoder_pred", "conv3x3", "lic_stack", "pack_lic_stack_weight", "lic_stack_fits", "gc_slices", "eb_likelihood", "eb_aux_loss",
     "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "dtype_code", "gc_slices_code", "gc_indexes",
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
+    "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "mae_loss", "TMAE_F32", "TMAE_BF16", "ACT_NONE", "ACT_GELU",
 ]
 
@@ -516,6 +517,46 @@ def invert_permutation(perm):
     inv = torch.empty_like(p)
     _lib.call("tmae_invert_permutation", p.data_ptr(), inv.data_ptr(), n, L, _stream())
     return inv
+
+
+def rans_stream_cap_words(nsymbols: int) -> int:
+    """words that always hold one stream of nsymbols symbols (no device work)"""
+    return int(_lib.value("tmae_rans_stream_cap_words", int(nsymbols)))
+
+
+def _rans_tables(tables):
+    cdf, sizes, offsets = tables
+    _need(cdf, torch.int32, "cdf")
+    _need(sizes, torch.int32, "cdf_sizes")
+    _need(offsets, torch.int32, "offsets")
+    if cdf.dim() != 2 or sizes.numel() != cdf.shape[0] or offsets.numel() != cdf.shape[0]:
+        raise ValueError("tables must be cdf [ncdf][stride], cdf_sizes [ncdf], offsets [ncdf]")
+    return cdf.data_ptr(), cdf.shape[1], sizes.data_ptr(), offsets.data_ptr(), cdf.shape[0]
+
+
+def rans_encode_streams(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap_words,
+                        nwords, status):
+    """code nstreams independent rANS streams on the device (csrc/rans_device.hip).  Stream b's segment j is
+    seg_len int32 at base + j * strides[0] + b * strides[1]; stream b lands in the last nwords[b] words of
+    slabs[b] (cap_words words each); status[b] != 0 where a slab was too small"""
+    _lib.call("tmae_rans_encode_streams", _p(symbols), sym_strides[0], sym_strides[1], _p(indexes), idx_strides[0],
+              idx_strides[1], nstreams, nseg, seg_len, *_rans_tables(tables), _p(slabs), cap_words, _p(nwords),
+              _p(status), _stream())
+
+
+def rans_pack_streams(slabs, cap_words, nwords, nstreams, dense, dense_cap_words, word_offsets, status):
+    """gather the slab tails into one dense word buffer; word_offsets int64 [nstreams + 1]"""
+    _lib.call("tmae_rans_pack_streams", _p(slabs), cap_words, _p(nwords), nstreams, _p(dense), dense_cap_words,
+              _p(word_offsets), _p(status), _stream())
+
+
+def rans_decode_streams(words, total_words, word_offsets, word_counts, indexes, idx_strides, symbols, sym_strides,
+                        nstreams, seg0, nseg, seg_len, tables, state, pos, status, first):
+    """decode segments [seg0, seg0 + nseg) of nstreams device-resident streams; state (int64 storage of the
+    uint64 coder state) / pos / status carry each stream from one call to the next"""
+    _lib.call("tmae_rans_decode_streams", _p(words), total_words, _p(word_offsets), _p(word_counts), _p(indexes),
+              idx_strides[0], idx_strides[1], _p(symbols), sym_strides[0], sym_strides[1], nstreams, seg0, nseg,
+              seg_len, *_rans_tables(tables), _p(state), _p(pos), _p(status), int(bool(first)), _stream())
 
 
 def _eb_params(eb) -> EBParams:

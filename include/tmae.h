@@ -395,6 +395,27 @@ int tmae_rans_decode_streams(const uint32_t* words, long long total_words, const
                              int ncdf, unsigned long long* state, int32_t* pos, int32_t* status, int first,
                              void* stream);
 
+/* Lane-interleaved records (MCM.compress_batch(lanes=L)): a stream's symbols are dealt round-robin over
+ * L = lanes sub-streams, L a power of two in 1..64.  Sub-stream l of stream b codes, segment after segment, the
+ * symbols k = l (mod L) of each segment with k ascending, and is byte for byte what the host coder writes for
+ * that subsequence (a sub-stream without symbols is the 8-byte flush of state 2^31).  Sub-stream b * L + l is one
+ * thread, a wave holds 64 / L whole streams.  A record is, for L >= 2, the words [L, count_0 .. count_{L-1}]
+ * followed by the sub-streams in lane order (assembled and parsed on the host, coder.py); L = 1 is the plain stream.
+ * nwords / word_offsets / word_counts / state / pos are per sub-stream ([nstreams * lanes], stream-major), status
+ * is per stream ([nstreams]): the maximum over its lanes; a stream with a status has nwords = 0 in every lane. */
+int tmae_rans_encode_lanes(const int32_t* symbols, long long sym_seg_stride, long long sym_stream_stride,
+                           const int32_t* indexes, long long idx_seg_stride, long long idx_stream_stride,
+                           int nstreams, int nseg, int seg_len, const int32_t* cdfs, int cdf_stride,
+                           const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
+                           long long cap_words, int32_t* nwords, int32_t* status, int lanes, void* stream);
+int tmae_rans_decode_lanes(const uint32_t* words, long long total_words, const long long* word_offsets,
+                           const int32_t* word_counts, const int32_t* indexes, long long idx_seg_stride,
+                           long long idx_stream_stride, int32_t* symbols, long long sym_seg_stride,
+                           long long sym_stream_stride, int nstreams, int seg0, int nseg, int seg_len,
+                           const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets,
+                           int ncdf, unsigned long long* state, int32_t* pos, int32_t* status, int first, int lanes,
+                           void* stream);
+
 /* ---------------------------------------------------------------- Kodak eval harness (testing.py, §8f row 4)
  * HuffmanCoding (utils/huffman.py:6-171, host, no device work): the code table of a tensor of int64 values
  * (first-occurrence order, CPython heapq tie order, pre-order codes MSB-first in the low `lens` bits of

@@ -1,0 +1,449 @@
+"""Lane-interleaved rANS records coded on the GPU (rans_encode_lanes / rans_decode_lanes in csrc/rans_device.hip) and
+MCM.compress_batch / decompress_batch with lanes > 1.
+
+Every comparison is an equality against the host coder: a record is what textmae_amd.coder.encode_record builds
+from RansEncoder's strings for the lanes' subsequences, and decoding returns the symbols that went in.  Kernel tests
+use the real GaussianConditional tables (64 rows, 3 to ~3 k entries wide) and the EntropyBottleneck tables of the
+SMALL12 model.
+"""
+import numpy as np
+import pytest
+import torch
+
+from oracle.mcm_oracle import MCMConfig, make_state_dict
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+FILL = 7777
+
+SMALL12 = dict(img_size=128, patch_size=16, encoder_embed_dim=128, encoder_depth=1, encoder_num_heads=2,
+               decoder_embed_dim=64, decoder_depth=1, decoder_num_heads=2, latent_depth=192, hyperprior_depth=96,
+               num_slices=12, num_keep_patches=16)
+
+
+def build(tmae, cfgd, seed, dtype=torch.float32):
+    cfg = MCMConfig(**cfgd)
+    m = tmae.MCM(**cfg.kwargs())
+    full = m.state_dict()
+    full.update(make_state_dict(cfg, seed))
+    m.load_state_dict(full)
+    m.compute_dtype = dtype
+    m = m.to(DEV).eval()
+    m.update(force=True)
+    return m
+
+
+def inputs(n, img, L, seed):
+    g = torch.Generator().manual_seed(seed)
+    imgs = (torch.rand(n, 3, img, img, generator=g) - 0.45) / 0.225
+    return imgs, torch.rand(n, L, generator=g)
+
+
+@pytest.fixture(scope="module")
+def gc(tmae):
+    from textmae_amd.entropy import GaussianConditional, get_scale_table
+
+    g = GaussianConditional(None).to(DEV)
+    g.update_scale_table(get_scale_table(), force=True)
+    sizes = g.host_tables()[1]
+    assert sizes.size == 64 and sizes.min() <= 8 and sizes.max() > 2048  # narrow and wide rows
+    return g
+
+
+@pytest.fixture(scope="module")
+def small(tmae):
+    return build(tmae, SMALL12, 11)
+
+
+def make_symbols(rng, idx, sizes, offsets, extremes=True, far_frac=0.05):
+    """~90 % inside the row's support, ~5 % 1..3 outside on either side, ~5 % (far_frac) |v| up to 2^20, two values
+    at +-2^27"""
+    maxv = sizes[idx].astype(np.int64) - 2  # values [0, maxv) are coded directly
+    off = offsets[idx].astype(np.int64)
+    v = off + (rng.random(idx.shape) * maxv).astype(np.int64)
+    u = rng.random(idx.shape)
+    k = rng.integers(1, 4, idx.shape)
+    side = rng.random(idx.shape) < 0.5
+    near = np.where(side, off - k, off + maxv - 1 + k)
+    far = rng.integers(-(1 << 20), (1 << 20) + 1, idx.shape)
+    v = np.where(u < 0.05, near, v)
+    v = np.where(u >= 1.0 - far_frac, far, v)
+    if extremes and v.size >= 8:
+        flat = v.reshape(-1)
+        flat[flat.size // 3] = 1 << 27
+        flat[2 * flat.size // 3] = -(1 << 27)
+    return v.astype(np.int32)
+
+
+class Case:
+    """nstreams x nseg x seg_len symbols / indexes in strided device buffers: symbols [segment][stream][seg_len] as
+    the model lays them out, indexes with padded strides of their own (or one shared array, stream stride 0)"""
+
+    def __init__(self, model, nstreams, nseg, seg_len, seed, idx=None, far_frac=0.05):
+        rng = np.random.default_rng(seed)
+        self.tabs_h = model.host_tables()
+        self.tabs = model.device_tables()
+        cdf, sizes, offsets = self.tabs_h
+        self.shape = (nstreams, nseg, seg_len)
+        shared = idx is not None
+        self.idx_h = np.broadcast_to(idx, self.shape).copy() if shared else \
+            rng.integers(0, sizes.size, self.shape).astype(np.int32)
+        self.sym_h = make_symbols(rng, self.idx_h, sizes, offsets, far_frac=far_frac)
+        self.sym_strides = (nstreams * seg_len, seg_len)
+        sym = np.ascontiguousarray(self.sym_h.transpose(1, 0, 2))
+        if shared:
+            self.idx_strides = (seg_len, 0)
+            ibuf = np.ascontiguousarray(self.idx_h[0])
+        else:
+            ts = seg_len + 9
+            ss = nstreams * ts + 7
+            self.idx_strides = (ss, ts)
+            ibuf = np.full(nseg * ss, -1, dtype=np.int32)
+            for j in range(nseg):
+                for b in range(nstreams):
+                    ibuf[j * ss + b * ts:j * ss + b * ts + seg_len] = self.idx_h[b, j]
+        self.sym = torch.from_numpy(sym.reshape(-1)).to(DEV)
+        self.idx = torch.from_numpy(ibuf.reshape(-1)).to(DEV)
+        self._want = {}
+
+    def want(self, lanes):
+        """the host coder's records"""
+        from textmae_amd.coder import encode_record
+
+        if lanes not in self._want:
+            n, nseg, seg_len = self.shape
+            self._want[lanes] = [encode_record(self.sym_h[b], self.idx_h[b], nseg, seg_len, lanes, self.tabs_h)
+                                 for b in range(n)]
+        return self._want[lanes]
+
+    def encode(self, lanes):
+        from textmae_amd.coder import DeviceRansEncoder
+
+        n, nseg, seg_len = self.shape
+        return DeviceRansEncoder().encode_records(self.sym, self.sym_strides, self.idx, self.idx_strides, n, nseg,
+                                                  seg_len, self.tabs, lanes)
+
+    def decode(self, records, lanes, calls, first=0, count=None):
+        """decode `calls` = [(seg0, nseg), ...] -> symbols [stream][segment][seg_len] (numpy), status"""
+        from textmae_amd.coder import DeviceRansDecoder
+
+        n, nseg, seg_len = self.shape
+        count = n if count is None else count
+        dec = DeviceRansDecoder()
+        dec.set_records(records, lanes, DEV)
+        out = torch.full((nseg, n, seg_len), FILL, dtype=torch.int32, device=DEV)
+        for seg0, ns in calls:
+            dec.decode_records(first, count, self.idx[first * self.idx_strides[1]:], self.idx_strides,
+                               out.view(-1)[first * self.sym_strides[1]:], self.sym_strides, seg0, ns, seg_len,
+                               self.tabs)
+        return out.cpu().numpy().transpose(1, 0, 2), dec.status()
+
+    def tables_of(self, records, lanes):
+        """(words, word offsets, word counts) of the records' sub-streams, as set_records lays them out"""
+        from textmae_amd.coder import parse_record
+
+        offs, lens, base = [], [], 0
+        for r in records:
+            o, c = parse_record(r, lanes)
+            offs.append(o + base)
+            lens.append(c)
+            base += len(r) // 4
+        return (np.frombuffer(b"".join(records), dtype=np.int32).copy(), np.concatenate(offs).astype(np.int64),
+                np.concatenate(lens).astype(np.int32))
+
+
+@pytest.fixture(scope="module")
+def case1(gc):
+    return Case(gc, 3, 3, 111, seed=1)
+
+
+@pytest.mark.parametrize("lanes", [2, 16, 64])
+def test_encode_records_equal_host_coder(case1, lanes):
+    """test 1: 3 streams x 3 segments x 111 symbols, escapes up to 8 digits, narrow and wide rows"""
+    sym, idx = case1.sym_h, case1.idx_h
+    cdf, sizes, offsets = case1.tabs_h
+    v = sym.astype(np.int64) - offsets[idx]
+    esc = (v < 0) | (v >= sizes[idx] - 2)
+    assert 0.05 < esc.mean() < 0.2 and np.abs(sym.astype(np.int64)).max() == 1 << 27
+    assert sizes[idx].min() <= 8 and sizes[idx].max() > 2048
+    got = case1.encode(lanes)
+    for b in range(3):
+        assert got[b] == case1.want(lanes)[b], f"record {b}"
+
+
+def test_one_lane_through_the_lanes_entry(case1):
+    """test 2: lanes = 1 through rans_encode_lanes / rans_decode_lanes is encode_streams' format"""
+    from textmae_amd import ops
+    from textmae_amd.coder import DeviceRansEncoder
+
+    n, nseg, seg_len = case1.shape
+    plain = DeviceRansEncoder().encode_streams(case1.sym, case1.sym_strides, case1.idx, case1.idx_strides, n, nseg,
+                                               seg_len, case1.tabs)
+    assert plain == case1.want(1)
+    cap = ops.rans_stream_cap_words(nseg * seg_len)
+    slabs = torch.zeros((n, cap), dtype=torch.int32, device=DEV)
+    nwords = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+    status = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+    ops.rans_encode_lanes(case1.sym, case1.sym_strides, case1.idx, case1.idx_strides, n, nseg, seg_len, case1.tabs,
+                          slabs, cap, nwords, status, 1)
+    assert status.cpu().tolist() == [0] * n
+    slabs_h, nw = slabs.cpu().numpy(), nwords.cpu().numpy()
+    for b in range(n):
+        assert slabs_h[b, cap - nw[b]:].tobytes() == plain[b], f"stream {b}"
+    words, offs, lens = case1.tables_of(plain, 1)
+    out = torch.full((nseg, n, seg_len), FILL, dtype=torch.int32, device=DEV)
+    state = torch.zeros(n, dtype=torch.int64, device=DEV)
+    pos = torch.zeros(n, dtype=torch.int32, device=DEV)
+    ops.rans_decode_lanes(torch.from_numpy(words).to(DEV), words.size, torch.from_numpy(offs).to(DEV),
+                          torch.from_numpy(lens).to(DEV), case1.idx, case1.idx_strides, out, case1.sym_strides, n, 0,
+                          nseg, seg_len, case1.tabs, state, pos, status, True, 1)
+    assert status.cpu().tolist() == [0] * n
+    assert np.array_equal(out.cpu().numpy().transpose(1, 0, 2), case1.sym_h)
+
+
+@pytest.mark.parametrize("lanes", [8, 64])
+@pytest.mark.parametrize("seg_len", [1, 5, 63, 64, 65])
+def test_ragged_and_empty_lanes(gc, seg_len, lanes):
+    """test 3: segments that end inside a step, and lanes without any symbol (the 8-byte empty stream)"""
+    c = Case(gc, 2, 2, seg_len, seed=100 + seg_len)
+    want = c.want(lanes)
+    assert c.encode(lanes) == want
+    got, status = c.decode(want, lanes, [(0, 2)])
+    assert not status.any() and np.array_equal(got, c.sym_h)
+
+
+@pytest.mark.parametrize("nstreams,lanes", [(5, 16), (3, 64)])
+def test_streams_per_wave(gc, nstreams, lanes):
+    """test 4: 5 streams of 16 lanes (the second wave holds one stream and 48 idle threads), 3 waves of 64 lanes"""
+    c = Case(gc, nstreams, 2, 70, seed=40 + nstreams)
+    want = c.want(lanes)
+    assert c.encode(lanes) == want
+    got, status = c.decode(want, lanes, [(0, 2)])
+    assert not status.any() and np.array_equal(got, c.sym_h)
+
+
+@pytest.mark.parametrize("lanes", [2, 16, 64])
+def test_resumed_decode(case1, lanes):
+    """test 5: one call, one call per segment, two then one; and stream 1 alone"""
+    want = case1.want(lanes)
+    for calls in ([(0, 3)], [(0, 1), (1, 1), (2, 1)], [(0, 2), (2, 1)]):
+        got, status = case1.decode(want, lanes, calls)
+        assert not status.any() and np.array_equal(got, case1.sym_h), calls
+    got, status = case1.decode(want, lanes, [(0, 3)], first=1, count=1)
+    assert not status.any() and np.array_equal(got[1], case1.sym_h[1])
+    assert (got[0] == FILL).all() and (got[2] == FILL).all()  # the other streams' outputs are untouched
+
+
+@pytest.mark.parametrize("hw", [1, 9])
+def test_entropy_bottleneck_tables(small, hw):
+    """test 6: 96 channel-indexed CDFs, the index array shared by the streams (index stream stride 0), 4 lanes"""
+    eb = small.entropy_bottleneck
+    zidx = eb._channel_indexes(hw)
+    c = Case(eb, 2, 1, 96 * hw, seed=20 + hw, idx=zidx)
+    want = c.want(4)
+    assert c.encode(4) == want
+    got, status = c.decode(want, 4, [(0, 1)])
+    assert not status.any() and np.array_equal(got, c.sym_h)
+
+
+def decode_raw(case, words, offs, lens, lanes, idx=None):
+    """rans_decode_lanes on explicit tables, the output between two guard regions -> (guard, symbols, guard, status)"""
+    from textmae_amd import ops
+
+    n, nseg, seg_len = case.shape
+    G, body = 64, nseg * n * seg_len
+    buf = torch.full((G + body + G,), FILL, dtype=torch.int32, device=DEV)
+    state = torch.zeros(n * lanes, dtype=torch.int64, device=DEV)
+    pos = torch.zeros(n * lanes, dtype=torch.int32, device=DEV)
+    status = torch.zeros(n, dtype=torch.int32, device=DEV)
+    ops.rans_decode_lanes(torch.from_numpy(words).to(DEV), words.size, torch.from_numpy(offs).to(DEV),
+                          torch.from_numpy(lens).to(DEV), case.idx if idx is None else idx, case.idx_strides,
+                          buf[G:], case.sym_strides, n, 0, nseg, seg_len, case.tabs, state, pos, status, True, lanes)
+    h = buf.cpu().numpy()
+    return h[:G], h[G:G + body].reshape(nseg, n, seg_len).transpose(1, 0, 2), h[G + body:], status.cpu().numpy()
+
+
+def test_decode_bounds_short_sub_stream(case1):
+    """test 7a: lane 3 (of 4) of stream 1 loses its last 3 words in the tables; the word buffer keeps its size, so a reader
+    that ignored the length would see stale words, not unallocated memory.  That stream reports status 4: the lane's
+    symbols up to the missing words are right and zeros follow, its other lanes are untouched; the other streams
+    decode exactly and nothing around the output is written."""
+    lanes, bad = 4, 3
+    words, offs, lens = case1.tables_of(case1.want(lanes), lanes)
+    lens[1 * lanes + bad] -= 3
+    before, got, after, st = decode_raw(case1, words, offs, lens, lanes)
+    assert st.tolist() == [0, 4, 0]
+    assert np.array_equal(got[0], case1.sym_h[0]) and np.array_equal(got[2], case1.sym_h[2])
+    assert (before == FILL).all() and (after == FILL).all()
+    lane_of = np.broadcast_to(np.arange(111) % lanes, (3, 111))
+    assert np.array_equal(got[1][lane_of != bad], case1.sym_h[1][lane_of != bad])
+    g, w = got[1][:, bad::lanes].reshape(-1), case1.sym_h[1][:, bad::lanes].reshape(-1)
+    stop = int(np.flatnonzero(g != w)[0])
+    assert stop > g.size // 2 and not g[stop:].any()
+
+
+def test_decode_bounds_bad_index(case1):
+    """test 7b: an index of -1 inside stream 2 gives status 5 for that stream only"""
+    lanes = 16
+    n, nseg, seg_len = case1.shape
+    words, offs, lens = case1.tables_of(case1.want(lanes), lanes)
+    idx = case1.idx.clone()
+    idx[1 * case1.idx_strides[0] + 2 * case1.idx_strides[1] + 40] = -1  # segment 1, stream 2, symbol 40
+    before, got, after, st = decode_raw(case1, words, offs, lens, lanes, idx=idx)
+    assert st.tolist() == [0, 0, 5]
+    assert np.array_equal(got[0], case1.sym_h[0]) and np.array_equal(got[1], case1.sym_h[1])
+    assert (before == FILL).all() and (after == FILL).all()
+    assert np.array_equal(got[2][0], case1.sym_h[2][0]) and got[2][1, 40] == 0
+
+
+@pytest.mark.parametrize("lanes,seg_len", [(2, 111), (16, 888)])
+def test_encode_bounds(gc, lanes, seg_len):
+    """test 8: slabs of a quarter of the bound (13 bits per symbol) with a quarter of the symbols far escapes (more
+    than 16 bits per symbol on average, about 166 symbols per sub-stream), so every host sub-stream (asserted first)
+    is past its slab: every stream reports the overflow, no sub-stream has words, and the 16 guard
+    words before and after every stream's slabs (streams launched one by one) and around all of them (one launch)
+    are intact"""
+    from textmae_amd import ops
+    from textmae_amd.coder import parse_record
+
+    c = Case(gc, 3, 3, seg_len, seed=2, far_frac=0.25)
+    n, nseg = 3, 3
+    cap = ops.rans_stream_cap_words(nseg * ((seg_len + lanes - 1) // lanes)) // 4
+    for rec in c.want(lanes):
+        assert (parse_record(rec, lanes)[1] > cap).all()
+    G, PAT = 16, 0x5A5A5A5A
+    buf = torch.full((n, G + lanes * cap + G), PAT, dtype=torch.int32, device=DEV)
+    nwords = torch.full((n * lanes,), -1, dtype=torch.int32, device=DEV)
+    status = torch.zeros(n, dtype=torch.int32, device=DEV)
+    for b in range(n):
+        ops.rans_encode_lanes(c.sym[b * c.sym_strides[1]:], c.sym_strides, c.idx[b * c.idx_strides[1]:],
+                              c.idx_strides, 1, nseg, seg_len, c.tabs, buf[b, G:], cap, nwords[b * lanes:],
+                              status[b:], lanes)
+    buf_h = buf.cpu().numpy()
+    assert status.cpu().tolist() == [1] * n and nwords.cpu().tolist() == [0] * (n * lanes)
+    assert (buf_h[:, :G] == PAT).all() and (buf_h[:, G + lanes * cap:] == PAT).all()
+    buf = torch.full((G + n * lanes * cap + G,), PAT, dtype=torch.int32, device=DEV)
+    status.zero_()
+    ops.rans_encode_lanes(c.sym, c.sym_strides, c.idx, c.idx_strides, n, nseg, seg_len, c.tabs, buf[G:], cap, nwords,
+                          status, lanes)
+    buf_h = buf.cpu().numpy()
+    assert status.cpu().tolist() == [1] * n
+    assert (buf_h[:G] == PAT).all() and (buf_h[G + n * lanes * cap:] == PAT).all()
+
+
+# ------------------------------------------------------------------------------------------------ model
+@pytest.fixture(scope="module")
+def small_batch(small):
+    imgs, scores = inputs(3, 128, 64, 5)
+    x, s = imgs.to(DEV), scores.to(DEV)
+    with torch.no_grad():
+        plain = small.compress_batch(x, s)
+        out = small.compress_batch(x, s, lanes=8, z_lanes=2)
+        streams = {k: np.array(v) for k, v in small._exec.last_streams.items()}
+    return x, s, plain, out, streams
+
+
+def test_model_records_equal_host_coder(small, small_batch):
+    """test 9a: image b's y and z records are encode_record of that image's slice of last_streams"""
+    from textmae_amd.coder import encode_record
+
+    x, s, plain, out, st = small_batch
+    B, S = 3, SMALL12["num_slices"]
+    gc, eb = small.gaussian_conditional, small.entropy_bottleneck
+    assert out["lanes"] == (8, 2) and "lanes" not in plain and set(out) == set(plain) | {"lanes"}
+    y_records, z_records = out["string"]
+    assert len(y_records) == len(z_records) == B and tuple(out["shape"]) == (1, 1)
+    ysym, yidx = st["y_symbols"].reshape(S, B, -1), st["y_indexes"].reshape(S, B, -1)
+    zidx = eb._channel_indexes(1)
+    for b in range(B):
+        want = encode_record(ysym[:, b], yidx[:, b], S, ysym.shape[2], 8, gc.host_tables())
+        assert y_records[b] == want, f"y record of image {b}"
+        want = encode_record(st["z_symbols"][b], zidx, 1, zidx.size, 2, eb.host_tables())
+        assert z_records[b] == want, f"z record of image {b}"
+
+
+def test_model_round_trip_equals_one_lane(small, small_batch):
+    """test 9b: the reconstruction from the lane records is bit for bit the one from the plain records"""
+    x, s, plain, out, _ = small_batch
+    with torch.no_grad():
+        rec = small.decompress_batch(out["string"], out["shape"], out["ids_restore"], lanes=8, z_lanes=2)["x_hat"]
+        ref = small.decompress_batch(plain["string"], plain["shape"], plain["ids_restore"])["x_hat"]
+    assert torch.equal(out["ids_restore"], plain["ids_restore"])
+    assert torch.equal(rec, ref)
+
+
+def test_model_bad_header_names_image(small, small_batch):
+    """test 9c: a flipped header word or the wrong lanes argument is a ValueError naming the image"""
+    x, s, plain, out, _ = small_batch
+    y, z = [list(v) for v in out["string"]]
+    args = (out["shape"], out["ids_restore"])
+    w = np.frombuffer(y[1], dtype="<u4").copy()
+    w[3] ^= 1
+    with pytest.raises(ValueError, match="y stream of image 1"):
+        small.decompress_batch([y[:1] + [w.tobytes()] + y[2:], z], *args, lanes=8, z_lanes=2)
+    w = np.frombuffer(z[2], dtype="<u4").copy()
+    w[0] ^= 6
+    with pytest.raises(ValueError, match="z stream of image 2"):
+        small.decompress_batch([y, z[:2] + [w.tobytes()]], *args, lanes=8, z_lanes=2)
+    with pytest.raises(ValueError, match="y stream of image 0"):
+        small.decompress_batch([y, z], *args, lanes=16, z_lanes=2)
+    with pytest.raises(ValueError, match="z stream of image 0"):
+        small.decompress_batch([y, z], *args, lanes=8, z_lanes=4)
+    with pytest.raises(ValueError, match="y stream of image 0"):
+        small.decompress_batch(plain["string"], *args, lanes=8, z_lanes=2)
+    with pytest.raises(ValueError, match="power of two"):
+        small.compress_batch(x, s, lanes=3)
+
+
+def test_model_defaults_keep_the_plain_format(small, small_batch):
+    """test 9d: compress_batch(x, s) with the defaults still returns the host coder's per-image strings"""
+    from textmae_amd.coder import RansEncoder
+
+    x, s, plain, _, st = small_batch
+    B, S = 3, SMALL12["num_slices"]
+    gc, eb = small.gaussian_conditional, small.entropy_bottleneck
+    assert set(plain) == {"string", "shape", "ids_restore"}
+    ysym, yidx = st["y_symbols"].reshape(S, B, -1), st["y_indexes"].reshape(S, B, -1)
+    zidx = eb._channel_indexes(1)
+    for b in range(B):
+        want = RansEncoder().encode_with_indexes(ysym[:, b].reshape(-1), yidx[:, b].reshape(-1), *gc.host_tables())
+        assert plain["string"][0][b] == want, f"y string of image {b}"
+        assert plain["string"][1][b] == eb._code(st["z_symbols"][b].reshape(-1), zidx), f"z string of image {b}"
+
+
+def test_vitb_round_trip_equals_one_lane(tmae):
+    """test 10: ViT-B 256^2, K = 144, batch 2, bf16, 16 y lanes: same reconstruction as the plain records.  A stream
+    of W words carries its symbols' bits plus 32 to 64 bits of flush overhead (the final state is in [2^31, 2^63)), so
+    L sub-streams cost 4 L - 8 to 8 L - 4 bytes more than the plain stream, and the header 4 (L + 1)"""
+    m = build(tmae, dict(img_size=256, num_keep_patches=144), 3, torch.bfloat16)
+    imgs, scores = inputs(2, 256, 256, 9)
+    x, s = imgs.to(DEV), scores.to(DEV)
+    with torch.no_grad():
+        plain = m.compress_batch(x, s)
+        out = m.compress_batch(x, s, lanes=16)
+        ref = m.decompress_batch(plain["string"], plain["shape"], plain["ids_restore"])["x_hat"]
+        rec = m.decompress_batch(out["string"], out["shape"], out["ids_restore"], lanes=16)["x_hat"]
+    assert out["lanes"] == (16, 1) and out["string"][1] == plain["string"][1]
+    assert torch.equal(rec, ref)
+    for b in range(2):
+        extra = len(out["string"][0][b]) - len(plain["string"][0][b])
+        assert 4 * 17 + 4 * 16 - 8 - 4 <= extra <= 4 * 17 + 8 * 16 - 4 + 4, extra  # one word of slack either way
+
+
+def test_eval_harness_lanes(tmae):
+    """testing.inference(lanes=N) codes through compress_batch / decompress_batch: the same image quality as the
+    host path, and the rate larger by exactly the record overhead that bits_per_pixel sees (the y record's header
+    and extra flushes; z stays at one lane).  192^2: the harness's MS-SSIM needs more than 160 pixels a side."""
+    from textmae_amd.testing import inference
+
+    m = build(tmae, dict(SMALL12, img_size=192, num_keep_patches=64), 13)
+    g = torch.Generator().manual_seed(3)
+    img, score = torch.rand(1, 3, 192, 192, generator=g), torch.rand(1, 144, generator=g)
+    host = inference(m, img, None, score)
+    laned = inference(m, img, None, score, lanes=4)
+    assert laned["psnr"] == host["psnr"] and laned["ms-ssim"] == host["ms-ssim"]
+    with torch.no_grad():
+        y1 = m.compress_batch(img.to(DEV), score.to(DEV))["string"][0][0]
+        y4 = m.compress_batch(img.to(DEV), score.to(DEV), lanes=4)["string"][0][0]
+    assert 4 * 5 + 4 * 4 - 8 - 4 <= len(y4) - len(y1) <= 4 * 5 + 8 * 4 - 4 + 4
+    assert laned["bpp"] == pytest.approx(host["bpp"] + (len(y4) - len(y1)) * 8.0 / (192 * 192), rel=1e-12)

@@ -168,6 +168,8 @@ SIGNATURES = {
     "tmae_rans_encode_streams": [P, LL, LL, P, LL, LL, I, I, I, P, I, P, P, I, P, LL, P, P, P],
     "tmae_rans_pack_streams": [P, LL, P, I, P, LL, P, P, P],
     "tmae_rans_decode_streams": [P, LL, P, P, P, LL, LL, P, LL, LL, I, I, I, I, P, I, P, P, I, P, P, P, I, P],
+    "tmae_rans_encode_lanes": [P, LL, LL, P, LL, LL, I, I, I, P, I, P, P, I, P, LL, P, P, I, P],
+    "tmae_rans_decode_lanes": [P, LL, P, P, P, LL, LL, P, LL, LL, I, I, I, I, P, I, P, P, I, P, P, P, I, I, P],
     # Kodak eval harness: Huffman side info (host), metrics and the score-map producer (device)
     "tmae_huffman_build": [P, LL, P, P, P, I, ctypes.POINTER(I)],
     "tmae_huffman_encode": [P, LL, P, P, P, I, P, LL, ctypes.POINTER(LL)],

@@ -8,6 +8,10 @@ arrays are handed to the coder without per-element Python work.
 
 ``DeviceRansEncoder`` / ``DeviceRansDecoder`` code the same format on the GPU (csrc/rans_device.hip), many
 independent streams at once from and to device tensors: the coder of ``MCM.compress_batch`` / ``decompress_batch``.
+
+``encode_record`` / ``decode_record`` / ``parse_record`` are the host side of the lane-interleaved records
+(``compress_batch(lanes=L)``): a record is ``lanes`` ordinary streams behind a small header, each stream what
+``RansEncoder`` writes for that lane's share of the symbols.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ import torch
 from . import _lib
 
 __all__ = ["BufferedRansEncoder", "RansEncoder", "RansDecoder", "pmf_to_quantized_cdf", "DeviceRansEncoder",
-           "DeviceRansDecoder"]
+           "DeviceRansDecoder", "lane_split", "encode_record", "decode_record", "parse_record"]
 
 
 def _i32(x) -> np.ndarray:
@@ -133,6 +137,81 @@ class RansDecoder:
             self._close()
 
 
+# ------------------------------------------------------------------ lane-interleaved records (host side)
+# A stream's symbols ([nseg][seg_len]) are dealt round-robin over L = lanes sub-streams: sub-stream l codes, segment
+# after segment, the symbols k = l (mod L) of each segment, k ascending, with their own indexes.  Record, L >= 2
+# (little-endian 32-bit words): L, the L word counts (each >= 2), then the sub-streams in lane order.  L = 1 is
+# the plain stream without a header.
+EMPTY_STREAM = bytes([0, 0, 0, 0x80, 0, 0, 0, 0])  # the coder's flush of state 2^31: a sub-stream without symbols
+
+
+def check_lanes(lanes) -> int:
+    if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or int(lanes) not in (1, 2, 4, 8, 16, 32, 64):
+        raise ValueError(f"lanes = {lanes!r} must be a power of two in 1..64")
+    return int(lanes)
+
+
+def lane_split(a, nseg: int, seg_len: int, lanes: int) -> list:
+    """the lanes subsequences of a ([nseg * seg_len] values): lane l = a.reshape(nseg, seg_len)[:, l::lanes]"""
+    lanes = check_lanes(lanes)
+    a = np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a).reshape(-1)
+    if a.size != nseg * seg_len:
+        raise ValueError(f"{a.size} values but nseg * seg_len = {nseg} * {seg_len}")
+    a = a.reshape(nseg, seg_len)
+    return [np.ascontiguousarray(a[:, l::lanes]).reshape(-1) for l in range(lanes)]
+
+
+def _assemble_record(subs) -> bytes:
+    if len(subs) == 1:
+        return bytes(subs[0])
+    head = np.array([len(subs)] + [len(s) // 4 for s in subs], dtype="<u4")
+    return head.tobytes() + b"".join(bytes(s) for s in subs)
+
+
+def encode_record(symbols, indexes, nseg: int, seg_len: int, lanes: int, tables) -> bytes:
+    """the record of one stream, coded on the host (the oracle of the device coder); tables = (cdfs, sizes, offsets)"""
+    subs = [RansEncoder().encode_with_indexes(s, i, *tables)
+            for s, i in zip(lane_split(symbols, nseg, seg_len, lanes), lane_split(indexes, nseg, seg_len, lanes))]
+    return _assemble_record(subs)
+
+
+def parse_record(record, lanes: int):
+    """-> (offsets, counts): int64 word offsets into the record and int32 word counts of its lanes sub-streams"""
+    lanes = check_lanes(lanes)
+    n = len(record)
+    if n % 4:
+        raise ValueError(f"a record is a whole number of 32-bit words (got {n} bytes)")
+    if lanes == 1:
+        if n < 8:
+            raise ValueError(f"a stream is at least 8 bytes (got {n})")
+        return np.zeros(1, dtype=np.int64), np.array([n // 4], dtype=np.int32)
+    if n < 4 * (lanes + 1):
+        raise ValueError(f"record of {n} bytes is shorter than the header of {lanes} lanes")
+    head = np.frombuffer(record, dtype="<u4", count=lanes + 1).astype(np.int64)
+    if head[0] != lanes:
+        raise ValueError(f"record header says {int(head[0])} lanes, {lanes} expected")
+    counts = head[1:]
+    if (counts < 2).any():
+        raise ValueError(f"sub-stream {int(np.argmax(counts < 2))} of the record has {int(counts.min())} words (< 2)")
+    if lanes + 1 + int(counts.sum()) != n // 4:
+        raise ValueError(f"sub-stream lengths sum to {int(counts.sum())} words, the record holds {n // 4 - lanes - 1}")
+    offsets = lanes + 1 + np.concatenate([[0], np.cumsum(counts[:-1])])
+    return offsets.astype(np.int64), counts.astype(np.int32)
+
+
+def decode_record(record, indexes, nseg: int, seg_len: int, lanes: int, tables) -> np.ndarray:
+    """the nseg * seg_len symbols of a record, decoded on the host"""
+    record = bytes(record)
+    offsets, counts = parse_record(record, lanes)
+    out = np.empty((nseg, seg_len), dtype=np.int32)
+    dec = RansDecoder()
+    for l, idx in enumerate(lane_split(indexes, nseg, seg_len, lanes)):
+        dec.set_stream(record[4 * int(offsets[l]):4 * (int(offsets[l]) + int(counts[l]))])
+        out[:, l::lanes] = dec.decode_stream_array(idx, *tables).reshape(nseg, -1)
+    dec._close()
+    return out.reshape(-1)
+
+
 # ------------------------------------------------------------------ per-image streams coded on the device
 # (csrc/rans_device.hip): the same format as the classes above, one independent stream per image, one wave each.
 STREAM_STATUS = {1: "output buffer too small", 2: "corrupt stream (symbol outside its CDF row)",
@@ -187,13 +266,57 @@ class DeviceRansEncoder:
         return [raw[4 * int(offs_h[b]):4 * (int(offs_h[b]) + int(nw_h[b]))] for b in range(nstreams)]
 
 
+    def _lane_buffers(self, device, nstreams, lanes, cap):
+        key = (device, nstreams, lanes, cap)
+        bufs = self._bufs.get(key)
+        if bufs is None:
+            nsub = nstreams * lanes
+            slabs = torch.empty((nsub, cap), dtype=torch.int32, device=device)
+            dense = torch.empty(nsub * cap, dtype=torch.int32, device=device)
+            # one small D2H: int64 word offsets [nsub + 1] | int32 nwords [nsub] | pack status [nsub] | status [nstreams]
+            meta = torch.empty(4 * nsub + 2 + nstreams, dtype=torch.int32, device=device)
+            bufs = self._bufs[key] = (slabs, dense, meta)
+        return bufs
+
+    def encode_records(self, symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, lanes,
+                       what="stream") -> list:
+        """encode_streams with every stream dealt over `lanes` sub-streams: one record (see encode_record) per
+        stream.  lanes = 1 is encode_streams itself.  The sub-streams are packed stream-major, lane-minor, so a
+        record's payload is one slice of the dense buffer; its header comes from the word counts on the host."""
+        from . import ops
+
+        lanes = check_lanes(lanes)
+        if lanes == 1:
+            return self.encode_streams(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, what)
+        nsub = nstreams * lanes
+        cap = ops.rans_stream_cap_words(nseg * ((seg_len + lanes - 1) // lanes))
+        slabs, dense, meta = self._lane_buffers(symbols.device, nstreams, lanes, cap)
+        offs = meta[:2 * nsub + 2].view(torch.int64)
+        nwords, pstatus, status = meta[2 * nsub + 2:3 * nsub + 2], meta[3 * nsub + 2:4 * nsub + 2], meta[4 * nsub + 2:]
+        pstatus.zero_()
+        ops.rans_encode_lanes(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap,
+                              nwords, status, lanes)
+        ops.rans_pack_streams(slabs, cap, nwords, nsub, dense, dense.numel(), offs, pstatus)
+        meta_h = meta.cpu().numpy()
+        offs_h = meta_h[:2 * nsub + 2].view(np.int64)
+        nw_h = meta_h[2 * nsub + 2:3 * nsub + 2].reshape(nstreams, lanes)
+        st_h = np.maximum(meta_h[4 * nsub + 2:], meta_h[3 * nsub + 2:4 * nsub + 2].reshape(nstreams, lanes).max(axis=1))
+        _raise_status(st_h, what)
+        raw = dense[:int(offs_h[nsub])].cpu().numpy().tobytes()  # payload-sized copy
+        head = np.concatenate([np.full((nstreams, 1), lanes, dtype=np.int32), nw_h], axis=1).astype("<u4")
+        return [head[b].tobytes() + raw[4 * int(offs_h[b * lanes]):4 * int(offs_h[(b + 1) * lanes])]
+                for b in range(nstreams)]
+
+
 class DeviceRansDecoder:
     """set_streams uploads every string with ONE H2D copy; decode_streams then maps device indexes to device
     symbols, any number of times per stream (each call carries on where the last one stopped), without touching
-    the host; check() reads the status words (the only synchronisation)."""
+    the host; check() reads the status words (the only synchronisation).  set_records / decode_records are the same
+    for lane-interleaved records (one status word per record)."""
 
     def __init__(self):
         self._n = 0
+        self._lanes = None  # per-record lane counts after set_records
 
     def set_streams(self, strings, device):
         n = len(strings)
@@ -221,6 +344,7 @@ class DeviceRansDecoder:
         self._pos = torch.zeros(n, dtype=torch.int32, device=device)
         self._status = torch.zeros(n, dtype=torch.int32, device=device)
         self._started = np.zeros(n, dtype=bool)
+        self._lanes = None
         self._n = n
 
     def decode_streams(self, first_stream, nstreams, indexes, idx_strides, symbols, sym_strides, seg0, nseg, seg_len,
@@ -230,7 +354,7 @@ class DeviceRansDecoder:
         from . import ops
 
         s0, s1 = int(first_stream), int(first_stream) + int(nstreams)
-        if self._n == 0:
+        if self._n == 0 or self._lanes is not None:
             raise ValueError("DeviceRansDecoder: set_streams() first")
         if not (0 <= s0 < s1 <= self._n):
             raise ValueError(f"streams [{s0}, {s1}) outside the {self._n} set")
@@ -241,6 +365,72 @@ class DeviceRansDecoder:
                                 symbols, sym_strides, s1 - s0, seg0, nseg, seg_len, tables, self._state[s0:s1],
                                 self._pos[s0:s1], self._status[s0:s1], not started.any())
         self._started[s0:s1] = True
+
+    def set_records(self, strings, lanes, device, what="record"):
+        """set_streams for lane-interleaved records: lanes is one lane count for every record or one per record.
+        The headers are parsed on the host (ValueError naming the record), the records go up whole in ONE copy, and
+        the sub-stream table points past the headers."""
+        n = len(strings)
+        if n == 0:
+            raise ValueError("DeviceRansDecoder: no records")
+        lanes = [check_lanes(lanes)] * n if isinstance(lanes, (int, np.integer)) else [check_lanes(v) for v in lanes]
+        if len(lanes) != n:
+            raise ValueError(f"{n} records but {len(lanes)} lane counts")
+        offs, lens, base = [], [], 0
+        for i, (s, L) in enumerate(zip(strings, lanes)):
+            try:
+                o, c = parse_record(s, L)
+            except ValueError as e:
+                raise ValueError(f"{what} {i}: {e}") from None
+            offs.append(o + base)
+            lens.append(c)
+            base += len(s) // 4
+        offs, lens = np.concatenate(offs), np.concatenate(lens)
+        nsub, total = offs.size, base
+        hdr = (12 * nsub + 7) // 8 * 8
+        buf = np.zeros(hdr + 4 * total, dtype=np.uint8)
+        buf[:8 * nsub] = offs.view(np.uint8)
+        buf[8 * nsub:12 * nsub] = lens.view(np.uint8)
+        buf[hdr:] = np.frombuffer(b"".join(bytes(s) for s in strings), dtype=np.uint8)
+        dev = torch.from_numpy(buf).to(device)  # the one upload
+        self._woff = dev[:8 * nsub].view(torch.int64)
+        self._wlen = dev[8 * nsub:12 * nsub].view(torch.int32)
+        self._words = dev[hdr:].view(torch.int32)
+        self._total = total
+        self._state = torch.zeros(nsub, dtype=torch.int64, device=device)
+        self._pos = torch.zeros(nsub, dtype=torch.int32, device=device)
+        self._status = torch.zeros(n, dtype=torch.int32, device=device)
+        self._started = np.zeros(n, dtype=bool)
+        self._lanes = np.array(lanes, dtype=np.int64)
+        self._sub0 = np.concatenate([[0], np.cumsum(self._lanes)])  # first sub-stream of every record
+        self._n = n
+
+    def decode_records(self, first_record, nrecords, indexes, idx_strides, symbols, sym_strides, seg0, nseg, seg_len,
+                       tables):
+        """decode_streams for records [first_record, first_record + nrecords) of set_records, which must share one
+        lane count; records of one lane are plain streams and take decode_streams' kernel"""
+        from . import ops
+
+        r0, r1 = int(first_record), int(first_record) + int(nrecords)
+        if self._n == 0 or getattr(self, "_lanes", None) is None:
+            raise ValueError("DeviceRansDecoder: set_records() first")
+        if not (0 <= r0 < r1 <= self._n):
+            raise ValueError(f"records [{r0}, {r1}) outside the {self._n} set")
+        L = int(self._lanes[r0])
+        if (self._lanes[r0:r1] != L).any():
+            raise ValueError("DeviceRansDecoder: records of one call must have one lane count")
+        started = self._started[r0:r1]
+        if started.any() != started.all():
+            raise ValueError("DeviceRansDecoder: records of one call must have been decoded equally far")
+        s0, s1 = int(self._sub0[r0]), int(self._sub0[r1])
+        args = (self._words, self._total, self._woff[s0:s1], self._wlen[s0:s1], indexes, idx_strides, symbols,
+                sym_strides, r1 - r0, seg0, nseg, seg_len, tables, self._state[s0:s1], self._pos[s0:s1],
+                self._status[r0:r1], not started.any())
+        if L == 1:
+            ops.rans_decode_streams(*args)
+        else:
+            ops.rans_decode_lanes(*args, L)
+        self._started[r0:r1] = True
 
     def status(self) -> np.ndarray:
         """per-stream status words (synchronises)"""

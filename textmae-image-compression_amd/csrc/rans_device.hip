@@ -413,6 +413,339 @@ rans_decode_streams_kernel(const uint32_t* __restrict__ words, long long total_w
   }
 }
 
+// ------------------------------------------------------------------------------------------------ lanes
+// Lane-interleaved records: a stream's symbols are dealt round-robin over L = 2^lg sub-streams (sub-stream l codes
+// the symbols k = l (mod L) of every segment, segments in order, k ascending), and every sub-stream is an ordinary
+// stream of the format above.  One THREAD per sub-stream: thread t of a wave is lane l = t mod L of stream
+// blockIdx.x * (64 / L) + t / L, so a wave holds 64 / L whole streams and lane l reads element step * L + l of a
+// segment (coalesced).  State, slab tail / word cursor and escape handling are per-thread registers in plain
+// divergent code; the loads are software-pipelined over the steps exactly as the kernels above pipeline chunks.
+// A stream's status is the maximum over its lanes (a shuffle reduction, then one store by lane 0).
+struct LaneEnc {
+  uint64_t x;
+  int head;  // words [head, cap) of the slab are written
+  int st;
+};
+
+__device__ __forceinline__ void lane_emit(LaneEnc& e, uint32_t* __restrict__ slab) {
+  if (e.head <= 0) {  // the slab is full: stop this sub-stream, never write outside it
+    e.st = kStOverflow;
+    return;
+  }
+  --e.head;
+  slab[e.head] = (uint32_t)e.x;
+  e.x >>= 32;
+}
+
+__device__ __forceinline__ void lane_put_bits(LaneEnc& e, uint32_t* __restrict__ slab, uint32_t val) {
+  if (e.st) return;
+  if (e.x >= (1ull << 59)) lane_emit(e, slab);
+  if (e.st) return;
+  e.x = (e.x << 4) | val;
+}
+
+__device__ __forceinline__ int group_max(int v, int L) {
+  for (int m = 1; m < L; m <<= 1) v = max(v, __shfl_xor(v, m, kWave));
+  return v;
+}
+
+__global__ void __launch_bounds__(kWave)
+rans_encode_lanes_kernel(const int* __restrict__ sym, long long sym_ss, long long sym_ts, const int* __restrict__ idx,
+                         long long idx_ss, long long idx_ts, int nstreams, int nseg, int seg_len,
+                         const int* __restrict__ cdfs, int cdf_stride, const int* __restrict__ sizes,
+                         const int* __restrict__ offs, int ncdf, uint32_t* __restrict__ slabs, long long cap,
+                         int* __restrict__ nwords, int* __restrict__ status, int lg) {
+  const int L = 1 << lg, t = threadIdx.x;
+  const int b = blockIdx.x * (kWave >> lg) + (t >> lg), l = t & (L - 1);
+  const bool active = b < nstreams;
+  const long long q = active ? (long long)b * L + l : 0;
+  uint32_t* __restrict__ slab = slabs + (size_t)q * cap;
+  const int* __restrict__ symb = sym + (active ? b * sym_ts : 0);
+  const int* __restrict__ idxb = idx + (active ? b * idx_ts : 0);
+  LaneEnc e{kRansLow, (int)cap, 0};
+  const int nsteps = (seg_len + L - 1) >> lg;  // steps per segment; lane l has a symbol in step s if s * L + l < seg_len
+  const int T = nseg * nsteps;
+  // pipeline registers, one step per stage, steps in reverse (last segment, last step first).  Stage A: index and
+  // symbol; B: the row's size and offset; C: clamp / escape and the two cdf entries; D: reciprocal, then the put.
+  int aj = nseg - 1, as = nsteps - 1;
+  int a_ci = 0, a_v = 0;
+  bool a_ok = false;
+  int b_ci = 0, b_v = 0, b_size = 3, b_off = 0;
+  bool b_ok = false, b_bad = false;
+  uint32_t c_start = 0, c_next = 1, c_raw = 0, c_flags = 0;  // flags: escaped | ndig << 1 | bad index << 8 | valid << 9
+  for (int it = 0; it < T + 3; ++it) {
+    // ---- D: fields of the symbol put in this iteration, from the cdf entries loaded one iteration ago
+    const uint32_t freq = c_next - c_start;
+    uint32_t shift = 0;
+    uint64_t rcp = ~0ull;
+    uint32_t d_bias = c_start + (1u << 16) - 1;  // freq 1: q = x - 1, so x + bias + q (2^16 - 1) = (x << 16) + start
+    if (freq >= 2) {
+      rcp = enc_reciprocal(freq, shift);
+      d_bias = c_start;
+    }
+    const uint32_t d_raw = c_raw, d_flags = c_flags;
+    // ---- C: clamp and escape the value, issue the loads of cdf[value] and cdf[value + 1]
+    c_flags = 0;
+    c_start = 0;
+    c_next = 1;
+    if (b_ok) {
+      const int max_value = b_size - 2;
+      int value = (int)((uint32_t)b_v - (uint32_t)b_off);
+      uint32_t raw = 0, esc = 0, ndig = 0;
+      if (value < 0) {
+        raw = (uint32_t)(-2 * (long long)value - 1);
+        value = max_value;
+      } else if (value >= max_value) {
+        raw = (uint32_t)(2 * (long long)(value - max_value));
+        value = max_value;
+      }
+      if (value == max_value) {
+        esc = 1;
+        ndig = raw ? 8u - ((uint32_t)__clz((int)raw) >> 2) : 0u;  // nibbles up to the top non-zero one
+      }
+      const int* __restrict__ row = cdfs + (size_t)b_ci * cdf_stride;
+      c_start = (uint32_t)row[value];
+      c_next = (uint32_t)row[value + 1];
+      c_raw = raw;
+      c_flags = esc | (ndig << 1) | (b_bad ? 1u << 8 : 0u) | (1u << 9);
+    }
+    // ---- B: the row's size and offset (a bad index reads row 0 and is never put)
+    b_ok = a_ok;
+    if (a_ok) {
+      b_bad = a_ci < 0 || a_ci >= ncdf;
+      b_ci = b_bad ? 0 : a_ci;
+      b_v = a_v;
+      b_size = sizes[b_ci];
+      b_off = offs[b_ci];
+    }
+    // ---- A: index and symbol
+    a_ok = false;
+    if (it < T) {
+      const int k = (as << lg) + l;
+      a_ok = active && k < seg_len;
+      if (a_ok) {
+        a_ci = idxb[aj * idx_ss + k];
+        a_v = symb[aj * sym_ss + k];
+      }
+      if (--as < 0) {
+        as = nsteps - 1;
+        --aj;
+      }
+    }
+    // ---- put
+    if (!((d_flags >> 9) & 1u) || e.st) continue;
+    if ((d_flags >> 8) & 1u) {
+      e.st = kStIndex;
+      continue;
+    }
+    if (d_flags & 1u) {
+      const int ndig = (int)((d_flags >> 1) & 15u);
+      for (int d = 7; d >= 0; --d)
+        if (d < ndig) lane_put_bits(e, slab, (d_raw >> (4 * d)) & 15u);
+      lane_put_bits(e, slab, (uint32_t)ndig);
+      if (e.st) continue;
+    }
+    if ((uint32_t)(e.x >> 32) >= (freq << 15)) {  // x >= freq << 47
+      lane_emit(e, slab);
+      if (e.st) continue;
+    }
+    const uint64_t qd = __umul64hi(e.x, rcp) >> shift;
+    e.x = e.x + d_bias + qd * (uint64_t)((1u << 16) - freq);
+  }
+  // 8-byte state flush, low word first in the stream
+  if (active && e.st == 0) {
+    if (e.head < 2) {
+      e.st = kStOverflow;
+    } else {
+      e.head -= 2;
+      slab[e.head + 1] = (uint32_t)(e.x >> 32);
+      slab[e.head] = (uint32_t)e.x;
+    }
+  }
+  const int st = group_max(active ? e.st : 0, L);
+  if (active) {
+    nwords[q] = st ? 0 : (int)cap - e.head;
+    if (l == 0) status[b] = st;
+  }
+}
+
+struct LaneDec {
+  uint64_t x;
+  int pos, len;    // next word to read, words in the sub-stream
+  uint32_t nextw;  // words[pos] while pos < len: loaded when the word before it was taken
+  int st;
+};
+
+__device__ __forceinline__ uint32_t lane_next_word(LaneDec& d, const uint32_t* __restrict__ w) {
+  if (d.pos < 0 || d.pos >= d.len) {
+    d.st = kStOverrun;
+    return 0;
+  }
+  const uint32_t r = d.nextw;
+  ++d.pos;
+  d.nextw = d.pos < d.len ? w[d.pos] : 0u;
+  return r;
+}
+
+__device__ __forceinline__ uint32_t lane_get_bits4(LaneDec& d, const uint32_t* __restrict__ w) {
+  const uint32_t v = (uint32_t)(d.x & 15u);
+  d.x >>= 4;
+  if (d.x < kRansLow) d.x = (d.x << 32) | lane_next_word(d, w);
+  return v;
+}
+
+__global__ void __launch_bounds__(kWave)
+rans_decode_lanes_kernel(const uint32_t* __restrict__ words, long long total_words, const long long* __restrict__ woff,
+                         const int* __restrict__ wlen, const int* __restrict__ idx, long long idx_ss, long long idx_ts,
+                         int* __restrict__ out, long long out_ss, long long out_ts, int nstreams, int seg0, int nseg,
+                         int seg_len, const int* __restrict__ cdfs, int cdf_stride, const int* __restrict__ sizes,
+                         const int* __restrict__ offs, int ncdf, int win_rows, unsigned long long* __restrict__ state,
+                         int* __restrict__ pos, int* __restrict__ status, int first, int lg) {
+  extern __shared__ int s_win[];  // [win_rows][64]: entries win_start(size) + i of each row, INT_MAX past its end
+  const int L = 1 << lg, t = threadIdx.x;
+#pragma unroll 4
+  for (int r = 0; r < win_rows; ++r) {
+    const int size = sizes[r], ent = win_start(size) + t;
+    s_win[r * kWave + t] = ent < size ? cdfs[(size_t)r * cdf_stride + ent] : INT_MAX;
+  }
+  __syncthreads();
+
+  const int b = blockIdx.x * (kWave >> lg) + (t >> lg), l = t & (L - 1);
+  const bool active = b < nstreams;
+  const long long q = active ? (long long)b * L + l : 0;
+  LaneDec d{0, 0, 0, 0u, 0};
+  long long off = 0;
+  if (active) {
+    d.st = first ? 0 : status[b];
+    off = woff[q];
+    d.len = wlen[q];
+    if (d.st == 0 && (off < 0 || d.len < 2 || off + d.len > total_words)) d.st = kStStream;
+  }
+  const uint32_t* __restrict__ w = words + (active && d.st == 0 ? off : 0);  // read only while st == 0
+  if (active && d.st == 0) {
+    if (first) {
+      d.x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+      d.pos = 2;
+    } else {
+      d.x = state[q];
+      d.pos = pos[q];
+      if (d.pos < 2 || d.pos > d.len) d.st = kStStream;
+    }
+    if (d.st == 0) d.nextw = d.pos < d.len ? w[d.pos] : 0u;
+  }
+  const int* __restrict__ idxb = idx + (active ? b * idx_ts : 0);
+  int* __restrict__ outb = out + (active ? b * out_ts : 0);
+
+  const int nsteps = (seg_len + L - 1) >> lg;
+  const int T = nseg * nsteps;
+  // pipeline registers.  Stage A: the index of a step; B: its row's size and offset; then the step itself.
+  int aj = 0, as = 0;
+  int a_ci = 0;
+  long long a_o = 0;
+  bool a_ok = false;
+  int b_ci = 0, b_size = 3, b_off = 0;
+  long long b_o = 0;
+  bool b_ok = false, b_bad = false;
+  for (int it = 0; it < T + 2; ++it) {
+    const int ci = b_ci, size = b_size, off_l = b_off;
+    const long long o = b_o;
+    const bool ok = b_ok, bad = b_bad;
+    b_ok = a_ok;
+    if (a_ok) {
+      b_bad = a_ci < 0 || a_ci >= ncdf;
+      b_ci = b_bad ? 0 : a_ci;
+      b_o = a_o;
+      b_size = sizes[b_ci];
+      b_off = offs[b_ci];
+    }
+    a_ok = false;
+    if (it < T) {
+      const int k = (as << lg) + l;
+      a_ok = active && k < seg_len;
+      if (a_ok) {
+        a_ci = idxb[(seg0 + aj) * idx_ss + k];
+        a_o = (seg0 + aj) * out_ss + k;
+      }
+      if (++as == nsteps) {
+        as = 0;
+        ++aj;
+      }
+    }
+    if (!ok) continue;
+    // ---- one symbol of this lane's sub-stream (zeros from the failing symbol on)
+    int outv = 0;
+    if (d.st == 0 && bad) d.st = kStIndex;
+    if (d.st == 0) {
+      const int cum = (int)(d.x & 0xFFFFu);
+      int s = -1, start = 0, next = 0;
+      bool found = false;
+      if (ci < win_rows) {  // 6-step binary search of the row's centre window: cnt = entries <= cum of its first 63
+        const int* win = s_win + ci * kWave;
+        const int last = win[kWave - 1];
+        int cnt = 0;
+#pragma unroll
+        for (int h = kWave / 2; h > 0; h >>= 1)
+          if (win[cnt + h - 1] <= cum) cnt += h;
+        if (cnt >= 1 && last > cum) {
+          s = win_start(size) + cnt - 1;
+          start = win[cnt - 1];
+          next = win[cnt];
+          found = true;
+        }
+      }
+      if (!found) {  // binary search over the whole row: 12 halvings cover 4096 entries
+        const int* __restrict__ row = cdfs + (size_t)ci * cdf_stride;
+        int lo = 0, n = size;
+        for (int i = 0; i < 12; ++i) {
+          if (n > 1) {
+            const int half = n >> 1;
+            if (row[lo + half] <= cum) {
+              lo += half;
+              n -= half;
+            } else {
+              n = half;
+            }
+          }
+        }
+        if (n == 1 && lo <= size - 2) {
+          start = row[lo];
+          next = row[lo + 1];
+          if (start <= cum && cum < next) s = lo;
+        }
+      }
+      if (s < 0 || s > size - 2) {
+        d.st = kStSymbol;
+      } else {
+        // advance: x = freq * (x >> 16) + (x & 0xFFFF) - start, then renormalise
+        d.x = (uint64_t)(uint32_t)(next - start) * (d.x >> 16) + (uint64_t)(uint32_t)cum - (uint32_t)start;
+        if (d.x < kRansLow) d.x = (d.x << 32) | lane_next_word(d, w);
+        int value = s;
+        const int max_value = size - 2;
+        if (s == max_value && d.st == 0) {
+          const uint32_t ndig = lane_get_bits4(d, w);  // 15 = "another count digit follows": more than 8 anyway
+          if (ndig > 8) {
+            d.st = kStEscape;
+          } else {
+            uint32_t raw = 0;
+            for (uint32_t g = 0; g < 8; ++g)
+              if (g < ndig && d.st == 0) raw |= lane_get_bits4(d, w) << (4 * g);
+            const int half = (int)(raw >> 1);
+            value = (raw & 1) ? -half - 1 : half + max_value;
+          }
+        }
+        if (d.st == 0) outv = (int)((uint32_t)value + (uint32_t)off_l);
+      }
+    }
+    outb[o] = outv;
+  }
+  const int st = group_max(active ? d.st : 0, L);
+  if (active) {
+    state[q] = d.x;
+    pos[q] = d.pos;
+    if (l == 0) status[b] = st;
+  }
+}
+
 }  // namespace
 
 // words that always hold a stream of n symbols.  With the state at or above 2^31 (2^27 for a bypass digit, after a
@@ -482,4 +815,64 @@ extern "C" int tmae_rans_decode_streams(const uint32_t* words, long long total_w
                      idx_stream_stride, symbols, sym_seg_stride, sym_stream_stride, seg0, nseg, seg_len, cdfs,
                      cdf_stride, cdf_sizes, offsets, ncdf, win_rows, state, pos, status, first ? 1 : 0);
   TMAE_LAUNCH_CHECK("tmae_rans_decode_streams");
+}
+
+// log2 of a lane count that is a power of two in 1..64, -1 otherwise
+static int lanes_log2(int lanes) {
+  for (int lg = 0; lg <= 6; ++lg)
+    if (lanes == 1 << lg) return lg;
+  return -1;
+}
+
+#define RANSD_LANES(name)                                                                                     \
+  const int lg = lanes_log2(lanes);                                                                           \
+  TMAE_REQUIRE(lg >= 0, name ": lanes = %d must be a power of two in 1..64", lanes);                          \
+  TMAE_REQUIRE((long long)nstreams * lanes <= INT32_MAX, name ": nstreams * lanes = %d * %d overflows int32", \
+               nstreams, lanes)
+
+extern "C" int tmae_rans_encode_lanes(const int32_t* symbols, long long sym_seg_stride, long long sym_stream_stride,
+                                      const int32_t* indexes, long long idx_seg_stride, long long idx_stream_stride,
+                                      int nstreams, int nseg, int seg_len, const int32_t* cdfs, int cdf_stride,
+                                      const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
+                                      long long cap_words, int32_t* nwords, int32_t* status, int lanes, void* stream) {
+  TMAE_REQUIRE(symbols && indexes && slabs && nwords && status, "tmae_rans_encode_lanes: NULL buffer");
+  RANSD_SHAPE("tmae_rans_encode_lanes");
+  RANSD_TABLES("tmae_rans_encode_lanes");
+  RANSD_LANES("tmae_rans_encode_lanes");
+  TMAE_REQUIRE(cap_words > 0 && cap_words <= INT32_MAX, "tmae_rans_encode_lanes: cap_words = %lld outside [1, 2^31)",
+               cap_words);
+  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
+               "tmae_rans_encode_lanes: negative stride");
+  const int per_wave = kWave >> lg;
+  hipLaunchKernelGGL(rans_encode_lanes_kernel, dim3((nstreams + per_wave - 1) / per_wave), dim3(kWave), 0,
+                     (hipStream_t)stream, symbols, sym_seg_stride, sym_stream_stride, indexes, idx_seg_stride,
+                     idx_stream_stride, nstreams, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf, slabs,
+                     cap_words, nwords, status, lg);
+  TMAE_LAUNCH_CHECK("tmae_rans_encode_lanes");
+}
+
+extern "C" int tmae_rans_decode_lanes(const uint32_t* words, long long total_words, const long long* word_offsets,
+                                      const int32_t* word_counts, const int32_t* indexes, long long idx_seg_stride,
+                                      long long idx_stream_stride, int32_t* symbols, long long sym_seg_stride,
+                                      long long sym_stream_stride, int nstreams, int seg0, int nseg, int seg_len,
+                                      const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                                      const int32_t* offsets, int ncdf, unsigned long long* state, int32_t* pos,
+                                      int32_t* status, int first, int lanes, void* stream) {
+  TMAE_REQUIRE(words && word_offsets && word_counts && indexes && symbols && state && pos && status,
+               "tmae_rans_decode_lanes: NULL buffer");
+  RANSD_SHAPE("tmae_rans_decode_lanes");
+  RANSD_TABLES("tmae_rans_decode_lanes");
+  RANSD_LANES("tmae_rans_decode_lanes");
+  TMAE_REQUIRE(total_words > 0 && seg0 >= 0, "tmae_rans_decode_lanes: total_words = %lld, seg0 = %d", total_words,
+               seg0);
+  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
+               "tmae_rans_decode_lanes: negative stride");
+  const int win_rows = ncdf < kMaxWinRows ? ncdf : kMaxWinRows;
+  const int per_wave = kWave >> lg;
+  hipLaunchKernelGGL(rans_decode_lanes_kernel, dim3((nstreams + per_wave - 1) / per_wave), dim3(kWave),
+                     (size_t)win_rows * kWave * sizeof(int), (hipStream_t)stream, words, total_words, word_offsets,
+                     word_counts, indexes, idx_seg_stride, idx_stream_stride, symbols, sym_seg_stride,
+                     sym_stream_stride, nstreams, seg0, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf,
+                     win_rows, state, pos, status, first ? 1 : 0, lg);
+  TMAE_LAUNCH_CHECK("tmae_rans_decode_lanes");
 }

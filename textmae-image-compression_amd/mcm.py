@@ -353,23 +353,35 @@ class MCM(CompressionModel):
             ex = self._executor(len(strings[1]), dev)
             return {"x_hat": ex.decompress(strings, shape, ids_restore)}
 
-    def compress_batch(self, imgs, total_scores):
+    def compress_batch(self, imgs, total_scores, lanes=1, z_lanes=None):
         """compress with one independent record per image, coded on the device (csrc/rans_device.hip) ->
         {"string": [y_strings, z_strings], "shape", "ids_restore"}, len(y_strings) == len(z_strings) == B.
         Image b's (y_strings[b], z_strings[b]) are the strings MCM.compress (MCM.py:805-894) returns for that image
-        alone.  Same preconditions as compress."""
+        alone.  Same preconditions as compress.
+
+        lanes / z_lanes (powers of two in 1..64, z_lanes=None: 1) deal an image's y / z symbols over that many
+        interleaved rANS states, which shortens the serial chain of the coder; the strings are then the records of
+        coder.encode_record, the result also carries "lanes": (lanes, z_lanes), and decompress_batch needs the same
+        values.  (1, 1) is the plain format above."""
+        from .coder import check_lanes
+
+        lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
         if not imgs.is_cuda:
             raise ValueError("MCM.compress_batch runs on the MI355X kernels: move the model and inputs to the GPU")
         self.entropy_bottleneck._check_cdf()
         self.gaussian_conditional._check_cdf()
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            return ex.compress_batch(imgs, total_scores)
+            return ex.compress_batch(imgs, total_scores, lanes, z_lanes)
 
-    def decompress_batch(self, strings, shape, ids_restore=None):
+    def decompress_batch(self, strings, shape, ids_restore=None, lanes=1, z_lanes=None):
         """inverse of compress_batch -> {"x_hat"}: strings = [y_strings, z_strings], one of each per image.  The
         streams are decoded on the device inside the slice loop; a corrupt stream raises ValueError naming its image
-        after the whole batch has been enqueued."""
+        after the whole batch has been enqueued.  lanes / z_lanes are compress_batch's; a record whose header does
+        not fit them raises ValueError naming its image before anything is launched."""
+        from .coder import check_lanes
+
+        lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
         assert isinstance(strings, list) and len(strings) == 2
         if ids_restore is None:
             raise ValueError("MCM.decompress_batch needs ids_restore (the decoder unshuffles by it, MCM.py:667-669)")
@@ -382,7 +394,7 @@ class MCM(CompressionModel):
             raise ValueError("MCM.decompress_batch runs on the MI355X kernels: move the model to the GPU")
         with torch.no_grad():
             ex = self._executor(len(strings[1]), dev)
-            return {"x_hat": ex.decompress_batch(strings, shape, ids_restore)}
+            return {"x_hat": ex.decompress_batch(strings, shape, ids_restore, lanes, z_lanes)}
 
 
 class _LazyStreams(collections.abc.Mapping):
@@ -715,9 +727,10 @@ class _Executor:
         shuf = ops.invert_permutation(ids_restore.to(self.device))
         return self._back(shuf, m.encoder_embed.proj.in_channels)
 
-    def compress_batch(self, imgs, scores):
+    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1):
         """compress with the device coder: the same symbol / index buffers, coded as one y and one z stream per
-        image (image b's y stream = its [slice][channel][pixel] symbols), the reference's batch-1 format B times"""
+        image (image b's y stream = its [slice][channel][pixel] symbols), the reference's batch-1 format B times;
+        with lanes / z_lanes > 1 a stream becomes a lane-interleaved record (coder.encode_record)"""
         from .coder import DeviceRansEncoder
 
         m, B = self.m, self.batch
@@ -736,12 +749,21 @@ class _Executor:
             enc = self._dev_encoder = DeviceRansEncoder()
         zidx = self._z_indexes()
         nz = N * hz * hz
-        z_strings = enc.encode_streams(zsym, (0, nz), zidx, (0, 0), B, 1, nz, eb.device_tables(),
-                                       what="z stream of image")
-        y_strings = enc.encode_streams(sym, (B * sw * HW, sw * HW), idx, (B * sw * HW, sw * HW), B, S, sw * HW,
-                                       gc.device_tables(), what="y stream of image")
+        if (lanes, z_lanes) == (1, 1):
+            z_strings = enc.encode_streams(zsym, (0, nz), zidx, (0, 0), B, 1, nz, eb.device_tables(),
+                                           what="z stream of image")
+            y_strings = enc.encode_streams(sym, (B * sw * HW, sw * HW), idx, (B * sw * HW, sw * HW), B, S, sw * HW,
+                                           gc.device_tables(), what="y stream of image")
+        else:
+            z_strings = enc.encode_records(zsym, (0, nz), zidx, (0, 0), B, 1, nz, eb.device_tables(), z_lanes,
+                                           what="z stream of image")
+            y_strings = enc.encode_records(sym, (B * sw * HW, sw * HW), idx, (B * sw * HW, sw * HW), B, S, sw * HW,
+                                           gc.device_tables(), lanes, what="y stream of image")
         self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # rate diagnostics
-        return {"string": [y_strings, z_strings], "shape": torch.Size([hz, hz]), "ids_restore": rest}
+        out = {"string": [y_strings, z_strings], "shape": torch.Size([hz, hz]), "ids_restore": rest}
+        if (lanes, z_lanes) != (1, 1):
+            out["lanes"] = (lanes, z_lanes)
+        return out
 
     def _z_indexes(self):
         """EntropyBottleneck channel indexes of one image's z symbols [C][hz*hz] on the device (shared by all images)"""
@@ -751,11 +773,11 @@ class _Executor:
             zidx = self._zidx = torch.from_numpy(zidx).to(self.device)
         return zidx
 
-    def decompress_batch(self, strings, shape, ids_restore):
+    def decompress_batch(self, strings, shape, ids_restore, lanes=1, z_lanes=1):
         """decompress of per-image records: every string goes up in one copy, the z and y streams are decoded by
         device kernels (the y streams inside the slice loop, one call per slice step), and nothing synchronises with
         the host until the status words are read after the last kernel of _back has been enqueued"""
-        from .coder import DeviceRansDecoder, _raise_status
+        from .coder import DeviceRansDecoder, _raise_status, parse_record
 
         m, B = self.m, self.batch
         N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
@@ -768,10 +790,22 @@ class _Executor:
         zidx = self._z_indexes()
         rest = ids_restore.to(self.device)
         dec = DeviceRansDecoder()
-        dec.set_streams(list(strings[0]) + list(strings[1]), self.device)  # streams [0, B): y, [B, 2B): z
+        laned = (lanes, z_lanes) != (1, 1)
+        if laned:  # headers are checked here, on the host, before the first launch
+            for part, L, name in ((strings[0], lanes, "y"), (strings[1], z_lanes, "z")):
+                for b, rec in enumerate(part):
+                    try:
+                        parse_record(rec, L)
+                    except ValueError as e:
+                        raise ValueError(f"{name} stream of image {b}: {e}") from None
+            dec.set_records(list(strings[0]) + list(strings[1]), [lanes] * B + [z_lanes] * B, self.device)
+            decode = dec.decode_records
+        else:
+            dec.set_streams(list(strings[0]) + list(strings[1]), self.device)  # streams [0, B): y, [B, 2B): z
+            decode = dec.decode_streams
         nz, per = N * hz * hz, B * sw * HW
         zsym = torch.empty((B, N, hz * hz), dtype=torch.int32, device=self.device)
-        dec.decode_streams(B, B, zidx, (0, 0), zsym, (0, nz), 0, 1, nz, etabs)
+        decode(B, B, zidx, (0, 0), zsym, (0, nz), 0, 1, nz, etabs)
         ops.eb_dequantize(eb, zsym, B, N, hz * hz, self.ZHAT, table=self.eb_table)
         self._h_s()
         idx = torch.empty(S * per, dtype=torch.int32, device=self.device)
@@ -780,7 +814,7 @@ class _Executor:
 
         def step(i0, nbs, mu, sigma, ms_stride):
             ops.gc_indexes(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:])
-            dec.decode_streams(0, B, idx, (per, sw * HW), sym, (per, sw * HW), i0, nbs, sw * HW, gtabs)
+            decode(0, B, idx, (per, sw * HW), sym, (per, sw * HW), i0, nbs, sw * HW, gtabs)
             ops.gc_dequantize(sym[i0 * per:], mu, ms_stride, sw, B, HW, nbs, sw, i0 * sw, self.SUPY, dt, M, self.YPRE,
                               M)
 

@@ -21,6 +21,7 @@ __all__ = [
     "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "dtype_code", "gc_slices_code", "gc_indexes",
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
+    "rans_encode_lanes", "rans_decode_lanes",
     "mae_loss", "TMAE_F32", "TMAE_BF16", "ACT_NONE", "ACT_GELU",
 ]
 
@@ -557,6 +558,71 @@ def rans_decode_streams(words, total_words, word_offsets, word_counts, indexes, 
     _lib.call("tmae_rans_decode_streams", _p(words), total_words, _p(word_offsets), _p(word_counts), _p(indexes),
               idx_strides[0], idx_strides[1], _p(symbols), sym_strides[0], sym_strides[1], nstreams, seg0, nseg,
               seg_len, *_rans_tables(tables), _p(state), _p(pos), _p(status), int(bool(first)), _stream())
+
+
+def _rans_lanes(lanes, nstreams, name):
+    """lanes must be a power of two in 1..64 -> sub-streams of the call"""
+    if isinstance(lanes, bool) or not isinstance(lanes, int) or lanes not in (1, 2, 4, 8, 16, 32, 64):
+        raise ValueError(f"{name}: lanes = {lanes!r} must be a power of two in 1..64")
+    if nstreams <= 0:
+        raise ValueError(f"{name}: nstreams = {nstreams} must be positive")
+    return nstreams * lanes
+
+
+def _rans_buf(t, dtype, numel, name, what):
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+    if t.numel() < numel:
+        raise ValueError(f"{name}: {what} holds {t.numel()} elements, {numel} needed")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be contiguous")
+
+
+def _rans_on_device(name, **tensors):
+    for what, t in tensors.items():
+        if not t.is_cuda:
+            raise ValueError(f"{name}: {what} must be a device (HIP) tensor")
+
+
+def rans_encode_lanes(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap_words,
+                      nwords, status, lanes):
+    """rans_encode_streams with every stream dealt over `lanes` sub-streams (sub-stream l of a stream codes the
+    symbols k = l mod lanes of each segment): sub-stream b * lanes + l lands in the last nwords[b * lanes + l]
+    words of slab b * lanes + l; status is per stream ([nstreams])"""
+    name = "rans_encode_lanes"
+    nsub = _rans_lanes(lanes, nstreams, name)
+    if cap_words <= 0:
+        raise ValueError(f"{name}: cap_words = {cap_words} must be positive")
+    _rans_buf(symbols, torch.int32, 1, name, "symbols")
+    _rans_buf(indexes, torch.int32, 1, name, "indexes")
+    _rans_buf(slabs, torch.int32, nsub * cap_words, name, "slabs")
+    _rans_buf(nwords, torch.int32, nsub, name, "nwords")
+    _rans_buf(status, torch.int32, nstreams, name, "status")
+    _rans_on_device(name, symbols=symbols, indexes=indexes, slabs=slabs, nwords=nwords, status=status)
+    _lib.call("tmae_rans_encode_lanes", _p(symbols), sym_strides[0], sym_strides[1], _p(indexes), idx_strides[0],
+              idx_strides[1], nstreams, nseg, seg_len, *_rans_tables(tables), _p(slabs), cap_words, _p(nwords),
+              _p(status), lanes, _stream())
+
+
+def rans_decode_lanes(words, total_words, word_offsets, word_counts, indexes, idx_strides, symbols, sym_strides,
+                      nstreams, seg0, nseg, seg_len, tables, state, pos, status, first, lanes):
+    """rans_decode_streams of lane-interleaved streams: word_offsets / word_counts / state / pos are per sub-stream
+    ([nstreams * lanes], stream-major), status per stream"""
+    name = "rans_decode_lanes"
+    nsub = _rans_lanes(lanes, nstreams, name)
+    _rans_buf(words, torch.int32, max(int(total_words), 1), name, "words")
+    _rans_buf(word_offsets, torch.int64, nsub, name, "word_offsets")
+    _rans_buf(word_counts, torch.int32, nsub, name, "word_counts")
+    _rans_buf(indexes, torch.int32, 1, name, "indexes")
+    _rans_buf(symbols, torch.int32, 1, name, "symbols")
+    _rans_buf(state, torch.int64, nsub, name, "state")
+    _rans_buf(pos, torch.int32, nsub, name, "pos")
+    _rans_buf(status, torch.int32, nstreams, name, "status")
+    _rans_on_device(name, words=words, word_offsets=word_offsets, word_counts=word_counts, indexes=indexes,
+                    symbols=symbols, state=state, pos=pos, status=status)
+    _lib.call("tmae_rans_decode_lanes", _p(words), total_words, _p(word_offsets), _p(word_counts), _p(indexes),
+              idx_strides[0], idx_strides[1], _p(symbols), sym_strides[0], sym_strides[1], nstreams, seg0, nseg,
+              seg_len, *_rans_tables(tables), _p(state), _p(pos), _p(status), int(bool(first)), lanes, _stream())
 
 
 def _eb_params(eb) -> EBParams:

@@ -71,21 +71,24 @@ def save_output(x, ori_shape, file_name, output_dir):
 
 
 @torch.no_grad()
-def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None):
-    """testing.py:60-100"""
+def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None, lanes=None):
+    """testing.py:60-100; lanes (--lanes N) codes through compress_batch / decompress_batch with N y lanes"""
     device = next(model.parameters()).device
     x = x.to(device)
     total_score = total_score.to(device)
     torch.cuda.synchronize()
     start = time.time()
-    out_enc = model.compress(x, total_score)
+    out_enc = model.compress(x, total_score) if lanes is None else model.compress_batch(x, total_score, lanes=lanes)
     enc_time = time.time() - start
     ids_keep = out_enc["ids_restore"]
     huffman = HuffmanCoding()
     compressed_ids_keep, shape, dev = huffman.compress(ids_keep)
     decompressed_ids_keep = huffman.decompress(compressed_ids_keep, shape, dev)
     start = time.time()
-    out_dec = model.decompress(out_enc["string"], out_enc["shape"], decompressed_ids_keep)
+    if lanes is None:
+        out_dec = model.decompress(out_enc["string"], out_enc["shape"], decompressed_ids_keep)
+    else:
+        out_dec = model.decompress_batch(out_enc["string"], out_enc["shape"], decompressed_ids_keep, lanes=lanes)
     torch.cuda.synchronize()
     dec_time = time.time() - start
     metrics = compute_metrics(x, out_dec["x_hat"], 255)
@@ -127,7 +130,7 @@ def load_test_images(paths, size=224):
     return out
 
 
-def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False):
+def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False, lanes=None):
     """testing.py:128-165 over pre-loaded (img [1,3,S,S], orig_shape) pairs and a [N, L] score tensor"""
     metrics = defaultdict(float)
     if output_dir is not None:
@@ -137,7 +140,7 @@ def eval_model(model, output_dir, images, scores, names=None, entropy_estimation
         if entropy_estimation:
             rv = inference_entropy_estimation(model, img, ts)
         else:
-            rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir)
+            rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir, lanes=lanes)
         for k, v in rv.items():
             metrics[k] += v
     for k in metrics:
@@ -171,6 +174,8 @@ def setup_args():
     p.add_argument("-c", "--checkpoint", dest="checkpoint_paths", type=str, nargs="*", required=True)
     p.add_argument("--num_keep_patches", type=int, default=144, required=True)
     p.add_argument("--input_size", type=int, default=224, required=True)
+    p.add_argument("--lanes", type=int, default=None, choices=[1, 2, 4, 8, 16, 32, 64],
+                   help="code on the device (compress_batch / decompress_batch) with this many interleaved y lanes")
     return p
 
 
@@ -195,7 +200,8 @@ def main(argv):
         if args.half:
             model.compute_dtype = torch.bfloat16
         model.update(force=True)
-        m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths], args.entropy_estimation)
+        m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths], args.entropy_estimation,
+                       lanes=args.lanes)
         for k, v in m.items():
             results[k].append(v)
     desc = "entropy estimation" if args.entropy_estimation else args.entropy_coder

@@ -5,9 +5,11 @@ MCM.compress_batch + decompress_batch (device rANS kernels, one y and one z stre
 ViT-B, 256 x 256, K = 144, bf16, seeded weights and inputs, at batch 64 and batch 1.  The two paths alternate in one
 process; each timed call is a wall clock around a device synchronise (both paths end in host bytes / a host
 status read anyway).  Prints ONE JSON line: medians and spread (min, max, interquartile range) of both paths per
-batch, and the bytes per image of both formats.
+batch, and the bytes per image of both formats.  --lanes 1,4,16,64 adds one device column per value above 1
+(compress_batch(lanes=N), lane-interleaved records; 1 is the plain device column), alternating with the others.
 
-    python tools/coding_bench.py [--rounds 10] [--warmup 3] [--batches 64,1] [--out profiles/coding_device/x.json]
+    python tools/coding_bench.py [--rounds 10] [--warmup 3] [--batches 64,1] [--lanes 1,4,16,64]
+                                 [--out profiles/coding_device/x.json]
 """
 import argparse
 import json
@@ -46,7 +48,7 @@ def stats(ms):
             "iqr_ms": round(q[2] - q[0], 3), "n": len(ms)}
 
 
-def run_batch(model, batch, img, rounds, warmup, dev):
+def run_batch(model, batch, img, rounds, warmup, dev, lanes=()):
     L = model.encoder_embed.num_patches
     x, s = inputs(batch, img, L, 1000, dev)
     paths = {
@@ -55,6 +57,11 @@ def run_batch(model, batch, img, rounds, warmup, dev):
         "device": (lambda: model.compress_batch(x, s),
                    lambda c: model.decompress_batch(c["string"], c["shape"], c["ids_restore"])),
     }
+    for n in lanes:
+        if n != 1:
+            paths[f"device_l{n}"] = (lambda n=n: model.compress_batch(x, s, lanes=n),
+                                     lambda c, n=n: model.decompress_batch(c["string"], c["shape"], c["ids_restore"],
+                                                                           lanes=n))
     t = {f"{p}_{k}": [] for p in paths for k in ("compress", "decompress")}
     rec, size = {}, {}
     with torch.no_grad():
@@ -66,8 +73,8 @@ def run_batch(model, batch, img, rounds, warmup, dev):
                     t[f"{p}_compress"].append(tc)
                     t[f"{p}_decompress"].append(td)
                 rec[p], size[p] = d["x_hat"], sum(len(b) for part in c["string"] for b in part) / batch
-    if not torch.equal(rec["host"], rec["device"]):
-        raise SystemExit("coding_bench: the two paths reconstruct different images")
+    if not all(torch.equal(rec["host"], rec[p]) for p in paths):
+        raise SystemExit("coding_bench: the paths reconstruct different images")
     out = {k: stats(v) for k, v in t.items()}
     for p in paths:
         total = [a + b for a, b in zip(t[f"{p}_compress"], t[f"{p}_decompress"])]
@@ -77,6 +84,11 @@ def run_batch(model, batch, img, rounds, warmup, dev):
     out["speedup_total"] = round(h["median_ms"] / d["median_ms"], 2)
     # faster by more than the run-to-run spread: the slowest device round beats the fastest host round
     out["device_faster_beyond_spread"] = bool(d["max_ms"] < h["min_ms"])
+    for p in paths:
+        if p.startswith("device_l"):  # against both yardsticks, by the same rule
+            v = out[f"{p}_total"]
+            out[f"{p}_faster_than_host_beyond_spread"] = bool(v["max_ms"] < h["min_ms"])
+            out[f"{p}_faster_than_device_beyond_spread"] = bool(v["max_ms"] < d["min_ms"])
     return out
 
 
@@ -88,10 +100,14 @@ def main():
     ap.add_argument("--img", type=int, default=256)
     ap.add_argument("--keep", type=int, default=144)
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
+    ap.add_argument("--lanes", default="", help="comma-separated y lane counts (powers of two up to 64)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if args.rounds < 2:
         ap.error("--rounds must be at least 2")
+    lanes = [int(v) for v in args.lanes.split(",") if v]
+    if any(n not in (1, 2, 4, 8, 16, 32, 64) for n in lanes):
+        ap.error("--lanes takes powers of two in 1..64")
 
     import textmae_amd
 
@@ -102,8 +118,10 @@ def main():
     model.update(force=True)
     res = {"tool": "coding_bench", "config": f"ViT-B img {args.img} K {args.keep} {args.dtype}",
            "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "warmup": args.warmup}
+    if lanes:
+        res["lanes"] = lanes
     for b in (int(v) for v in args.batches.split(",")):
-        res[f"batch_{b}"] = run_batch(model, b, args.img, args.rounds, args.warmup, dev)
+        res[f"batch_{b}"] = run_batch(model, b, args.img, args.rounds, args.warmup, dev, lanes)
     line = json.dumps(res)
     print(line)
     if args.out:

@@ -215,6 +215,11 @@ def unshuffle_bwd(dy, ldy, pre, ldp, out, n, H, W, C4, dtype, dy_f32):
               _stream())
 
 
+def gelu_bwd(dy, pre, out, total, dtype, dy_f32):
+    """out = dy * gelu'(pre) over `total` contiguous elements (pre / out in dtype, dy f32 or dtype)"""
+    _lib.call("tmae_gelu_bwd", _p(dy), int(dy_f32), _p(pre), _p(out), total, dtype_code(dtype), _stream())
+
+
 def lrp_bwd(t, ldt, dt, lddt, rows, C, dtype, g32=None, ld32=0, g16=None, ld16=0, gsum=None, ldgs=0, g32b=None,
             ld32b=0):
     _lib.call("tmae_lrp_bwd", _p(g32), ld32, _p(g32b), ld32b, _p(g16), ld16, _p(t), ldt, _p(dt), lddt, _p(gsum), ldgs,

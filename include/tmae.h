@@ -81,7 +81,10 @@ int tmae_patch_embed_gathered(const void* patches, const int64_t* ids_shuffle, c
 int tmae_cls_rows(float* tokens, const float* cls, const float* pos, int n, int rows_per_img, int D, void* stream);
 
 /* Fused multi-head attention over qkv [B*T][3*H*dh] (timm layout (3, H, dh)) -> out [B*T][H*dh];
- * softmax((q k^T) * scale) v, dh in {32, 64, 80} (80: ViT-H, models_mae.py:239-244), T <= 512. */
+ * softmax((q k^T) * scale) v, dh in {32, 64, 80} (80: ViT-H, models_mae.py:239-244), any T >= 1.  A head whose
+ * K and V fit LDS (T <= 512 at dh 32; bf16 480 at dh 64, 416 at dh 80; f32 288 at dh 64, 224 at dh 80) runs on
+ * the LDS-resident kernels; longer sequences run on kernels that stream K / V through LDS in chunks
+ * (tmae_mha_plan names the choice).  No workspace either way. */
 int tmae_mha_fwd(const void* qkv, void* out, int B, int T, int H, int dh, float scale, int dtype, void* stream);
 
 /* qkv Linear + multi-head attention in one launch (bf16 inference; timm Attention qkv + core, MCM.py:629-630,
@@ -471,10 +474,13 @@ int tmae_linear_fwd_pre(const void* x, int x_f32, int ldx, int row_group, int gr
 /* out = resid + x w^T + bias, out-of-place (autograd keeps the block input) */
 int tmae_linear_residual_out(const void* x, int ldx, const void* w, const float* bias, const float* resid, float* out,
                              int ld, int M, int N, int K, int dtype, void* stream);
-/* tmae_mha_fwd + the per-row log2-sum-exp lse[b][h][t] (base-2, of scores * scale * log2 e) */
+/* tmae_mha_fwd + the per-row log2-sum-exp lse[b][h][t] (base-2, of scores * scale * log2 e); the same array
+ * from the resident and the streamed kernels, so either forward feeds either backward */
 int tmae_mha_fwd_lse(const void* qkv, void* out, float* lse, int B, int T, int H, int dh, float scale, int dtype,
                      void* stream);
-/* timm Attention backward: dqkv [B*T][3*H*dh] (dtype) from qkv, o (forward output), dO, lse */
+/* timm Attention backward: dqkv [B*T][3*H*dh] (dtype) from qkv, o (forward output), dO, lse.  Any T >= 1: one
+ * LDS-resident launch where a head fits (bf16 dh 64 / 80 and f32 dh 80: T <= 256, otherwise T <= 512), else
+ * two streamed launches (dK / dV, then dQ).  No atomics and no workspace; bitwise reproducible. */
 int tmae_mha_bwd(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, int B, int T, int H,
                  int dh, float scale, int dtype, void* stream);
 /* kept-patch im2col for the patch-embed weight gradient: out[n*keep][Kw] (dtype), Kw = C*P*P rounded up to a
@@ -636,6 +642,18 @@ int tmae_gemm_plan(int M, int N, int K, int batch, int dtype, char* out, int len
  * chooser.  Returns the previous value; tmae_gemm_plan reflects it.  Not synchronised: set it from one thread,
  * between launches. */
 int tmae_gemm_force_tile(int index);
+
+/* diagnostics (no device work): writes into out[len] the attention kernel family tmae_mha_fwd / tmae_mha_fwd_lse
+ * (backward = 0) or tmae_mha_bwd (backward = 1) launch at sequence length T: the resident kernel's name, e.g.
+ * "mha_fwd_bf16_kernel<64>", or for the streamed family "stream<bf16,dh64,q256,c128>" (forward: queries per
+ * workgroup, keys per LDS chunk) / "stream<bf16,dh64,q128,k128,c128>" (backward: queries per workgroup of the dQ
+ * kernel, keys per workgroup of the dK / dV kernel, rows per LDS chunk of both). */
+int tmae_mha_plan(int T, int dh, int dtype, int backward, char* out, int len);
+
+/* test hook (host only, no device work): with on != 0 every tmae_mha_fwd / _lse / _bwd launch of this process
+ * takes the streamed family, whatever T.  Returns the previous value; tmae_mha_plan reflects it.  Not
+ * synchronised: set it from one thread, between launches. */
+int tmae_mha_force_stream(int on);
 
 #ifdef __cplusplus
 }

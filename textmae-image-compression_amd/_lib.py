@@ -144,6 +144,7 @@ SIGNATURES = {
     "tmae_crop_normalize_u8": [P, I, I, I, P, I, I, ctypes.POINTER(F), ctypes.POINTER(F), P, P],
     "tmae_bpp_sum": [P, LL, P, LL, P, P, ctypes.c_double, P],
     "tmae_gemm_plan": [I, I, I, I, I, ctypes.c_char_p, I],
+    "tmae_mha_plan": [I, I, I, I, ctypes.c_char_p, I],
     "tmae_mae_masking": [P, P, P, P, I, I, I, P],
     "tmae_mae_loss": [P, P, P, I, I, I, I, I, I, I, P, P, P],
     "tmae_mae_loss_bwd": [P, P, P, I, I, I, I, I, I, I, P, P, P, I, P],
@@ -224,6 +225,7 @@ VALUE_FUNCS = {"tmae_wgrad_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_image_scores_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_qkv_attn_supported": ([I, I, I], ctypes.c_int),
                "tmae_gemm_force_tile": ([I], ctypes.c_int),
+               "tmae_mha_force_stream": ([I], ctypes.c_int),
                "tmae_rans_stream_cap_words": ([LL], ctypes.c_longlong)}
 
 _lib = None

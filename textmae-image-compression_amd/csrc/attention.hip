@@ -13,6 +13,10 @@
 #include <stdlib.h>
 
 #include "attn_core.h"
+#include "attn_stream.h"
+
+// test hook (tmae_mha_force_stream): every tmae_mha_* launch takes the streamed family
+static int g_tmae_mha_force_stream = 0;
 
 template <typename T> struct AttnCfg;
 template <> struct AttnCfg<bf16> { static constexpr int KPAD = 8, VPAD = 4, EPC = 8; };
@@ -236,18 +240,33 @@ mha_fwd_bf16_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out, float*
                     out + (size_t)b * Tn * D + h * DH, D);
 }
 
+// The resident forward kernel a length gets (the launch geometry mha_launch uses) -- or none: K + V of the head
+// no longer fit LDS, or one wave per 32 queries no longer fits a workgroup.  Then the streamed family runs.
+struct MhaFwdPick { bool resident, lean; int nthr; size_t lds; };
 template <typename T, int DH>
-static int mha_launch(const void* qkv, void* out, int B, int Tn, int H, float scale, hipStream_t st,
-                      float* lse = nullptr) {
-  const int Tpad = (Tn + 31) / 32 * 32;
+static MhaFwdPick mha_fwd_pick(int Tn) {
+  const long long Tpad = ((long long)Tn + 31) / 32 * 32;
   constexpr bool lean_ok = sizeof(T) == 2 && DH % 32 == 0;  // the VALU-lean kernel takes whole 32-wide tiles
   constexpr int DHP = (DH + 31) / 32 * 32;
   const bool lean = lean_ok;  // the plain kernel: f32 and the ViT-H head dim 80 (lean: 18 vs 23 us enc, 30 vs 44 dec)
-  const int nthr = 64 * (Tpad / 32);
+  const long long nthr = 64 * (Tpad / 32);
   const size_t lds = lean ? ((size_t)Tpad * (DH + 8) + (size_t)Tpad * AttnTr<DH>::LDV) * 2
                           : ((size_t)Tpad * (DH + AttnCfg<T>::KPAD) + (size_t)DHP * (Tpad + AttnCfg<T>::VPAD)) * sizeof(T);
-  TMAE_REQUIRE(nthr <= 1024 && lds <= 160 * 1024, "tmae_mha_fwd: sequence length %d too long", Tn);
-  TMAE_REQUIRE(!lean || Tpad * (DH / 8) <= nthr * (DH / 16), "tmae_mha_fwd: sequence length %d too long", Tn);
+  const bool fits = (nthr <= 1024 && lds <= 160 * 1024) && (!lean || Tpad * (DH / 8) <= nthr * (DH / 16));
+  return MhaFwdPick{fits && !g_tmae_mha_force_stream, lean, (int)(fits ? nthr : 0), lds};
+}
+
+template <typename T, int DH>
+static int mha_launch(const void* qkv, void* out, int B, int Tn, int H, float scale, hipStream_t st,
+                      float* lse = nullptr) {
+  const MhaFwdPick pick = mha_fwd_pick<T, DH>(Tn);
+  if (!pick.resident)
+    return mha_stream_fwd(qkv, out, lse, B, Tn, H, DH, scale, sizeof(T) == 2 ? TMAE_BF16 : TMAE_F32, st);
+  const int Tpad = (Tn + 31) / 32 * 32;
+  constexpr bool lean_ok = sizeof(T) == 2 && DH % 32 == 0;
+  const bool lean = pick.lean;
+  const int nthr = pick.nthr;
+  const size_t lds = pick.lds;
   if (B * H == 0 || Tn == 0) return TMAE_OK;
   if constexpr (lean_ok) {
     if (lean) {
@@ -895,23 +914,45 @@ mha_bwd_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ o, c
 #endif
 template <int DH> struct AttnBwdOnePass { static constexpr bool value = DH == 32 || (DH == 64 && TMAE_BWD1_DH64); };
 
+// The resident backward kernel a length gets, or MHA_BWD_NONE: the streamed family runs.  One wave per 32 tokens
+// bounds every resident form; bf16 dh 64 / 80 are bounded at 512 threads, and so is f32 dh 80.
+enum { MHA_BWD_NONE = 0, MHA_BWD_ONEPASS, MHA_BWD_ONEPASS_640, MHA_BWD_TWOPHASE, MHA_BWD_F32 };
+struct MhaBwdPick { int kind, nthr; size_t lds; };
 template <int DH>
-static int mha_bwd_launch(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, int B, int Tn,
-                          int H, float scale, int dtype, hipStream_t st) {
-  const int Tpad = (Tn + 31) / 32 * 32;
-  const int nthr = 64 * (Tpad / 32);
-  TMAE_REQUIRE(nthr <= 1024, "tmae_mha_bwd: sequence length %d too long", Tn);
-  if (B * H == 0 || Tn == 0) return TMAE_OK;
+static MhaBwdPick mha_bwd_pick(int Tn, int dtype) {
+  const long long Tpad = ((long long)Tn + 31) / 32 * 32;
+  const long long nthr = 64 * (Tpad / 32);
+  if (g_tmae_mha_force_stream || !(nthr <= 1024)) return MhaBwdPick{MHA_BWD_NONE, 0, 0};
   if (dtype == TMAE_BF16) {
-    TMAE_REQUIRE(DH == 32 || nthr <= 512, "tmae_mha_bwd: sequence length %d too long for head dim %d", Tn, DH);
+    if (!(DH == 32 || nthr <= 512)) return MhaBwdPick{MHA_BWD_NONE, 0, 0};
     constexpr int LDR = AttnBwd<DH>::LDR;
     // Q, dO (and K unless dh 32 holds it in registers), dS scratch, dQ, lse / delta
     const size_t lds1 = (size_t)(DH == 32 ? 2 : 3) * Tpad * LDR * 2 + (size_t)(Tpad / 32) * 2048 +
                         (size_t)DH * (Tpad + 4) * 4 + (size_t)2 * Tpad * 4;
-    if (AttnBwdOnePass<DH>::value && lds1 <= 160 * 1024) {
+    if (AttnBwdOnePass<DH>::value && lds1 <= 160 * 1024)
+      return MhaBwdPick{DH == 32 && nthr > 512 && nthr <= 640 ? MHA_BWD_ONEPASS_640 : MHA_BWD_ONEPASS, (int)nthr, lds1};
+    const size_t lds = (size_t)2 * Tpad * LDR * 2 + (size_t)2 * Tpad * 4;
+    if (!(lds <= 160 * 1024)) return MhaBwdPick{MHA_BWD_NONE, 0, 0};
+    return MhaBwdPick{MHA_BWD_TWOPHASE, (int)nthr, lds};
+  }
+  if (!(DH != 80 || nthr <= 512)) return MhaBwdPick{MHA_BWD_NONE, 0, 0};
+  return MhaBwdPick{MHA_BWD_F32, (int)nthr, 0};
+}
+
+template <int DH>
+static int mha_bwd_launch(const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, int B, int Tn,
+                          int H, float scale, int dtype, hipStream_t st) {
+  const MhaBwdPick pick = mha_bwd_pick<DH>(Tn, dtype);
+  if (pick.kind == MHA_BWD_NONE) return mha_stream_bwd(qkv, o, dout, lse, dqkv, B, Tn, H, DH, scale, dtype, st);
+  const int Tpad = (Tn + 31) / 32 * 32;
+  const int nthr = pick.nthr;
+  if (B * H == 0 || Tn == 0) return TMAE_OK;
+  if (dtype == TMAE_BF16) {
+    if (pick.kind != MHA_BWD_TWOPHASE) {
+      const size_t lds1 = pick.lds;
       constexpr int D1 = AttnBwdOnePass<DH>::value ? DH : 32;
       constexpr int M9 = D1 == 32 ? 640 : 512;  // the 9-10-wave instance (dh 32 only)
-      if (D1 == 32 && nthr > 512 && nthr <= 640)
+      if (pick.kind == MHA_BWD_ONEPASS_640)
         hipLaunchKernelGGL((mha_bwd1_bf16_kernel<D1, M9>), dim3(B * H), dim3(nthr), lds1, st, (const bf16*)qkv,
                            (const bf16*)o, (const bf16*)dout, lse, (bf16*)dqkv, Tn, H, Tpad, scale);
       else
@@ -919,12 +960,10 @@ static int mha_bwd_launch(const void* qkv, const void* o, const void* dout, cons
                            (const bf16*)o, (const bf16*)dout, lse, (bf16*)dqkv, Tn, H, Tpad, scale);
       TMAE_LAUNCH_CHECK("tmae_mha_bwd");
     }
-    const size_t lds = (size_t)2 * Tpad * LDR * 2 + (size_t)2 * Tpad * 4;
-    TMAE_REQUIRE(lds <= 160 * 1024, "tmae_mha_bwd: sequence length %d needs %zu B of LDS", Tn, lds);
+    const size_t lds = pick.lds;
     hipLaunchKernelGGL((mha_bwd_bf16_kernel<DH>), dim3(B * H), dim3(nthr), lds, st, (const bf16*)qkv, (const bf16*)o,
                        (const bf16*)dout, lse, (bf16*)dqkv, Tn, H, Tpad, scale);
   } else {
-    TMAE_REQUIRE(DH != 80 || nthr <= 512, "tmae_mha_bwd: sequence length %d too long for head dim 80", Tn);
     hipLaunchKernelGGL((mha_bwd_f32_kernel<DH>), dim3(B * H), dim3(nthr), 0, st, (const float*)qkv, (const float*)o,
                        (const float*)dout, lse, (float*)dqkv, Tn, H, Tpad, scale);
   }
@@ -939,4 +978,49 @@ extern "C" int tmae_mha_bwd(const void* qkv, const void* o, const void* dout, co
   if (dh == 80) return mha_bwd_launch<80>(qkv, o, dout, lse, dqkv, B, T, H, scale, dtype, st);
   return dh == 64 ? mha_bwd_launch<64>(qkv, o, dout, lse, dqkv, B, T, H, scale, dtype, st)
                   : mha_bwd_launch<32>(qkv, o, dout, lse, dqkv, B, T, H, scale, dtype, st);
+}
+
+// ------------------------------------------------------------------ diagnostics
+template <int DH>
+static void mha_plan_t(int T, int dtype, int backward, char* out, int len) {
+  const bool bf = dtype == TMAE_BF16;
+  const char* dn = bf ? "bf16" : "f32";
+  if (!backward) {
+    const MhaFwdPick p = bf ? mha_fwd_pick<bf16, DH>(T) : mha_fwd_pick<float, DH>(T);
+    if (p.resident) {
+      if (p.lean) snprintf(out, len, "mha_fwd_bf16_kernel<%d>", DH);
+      else if (bf && DH == 80 && p.nthr <= 512) snprintf(out, len, "mha_fwd_kernel<bf16,80,512>");
+      else snprintf(out, len, "mha_fwd_kernel<%s,%d>", dn, DH);
+      return;
+    }
+    const MhaStreamSizes z = mha_stream_sizes(dtype, 0);
+    snprintf(out, len, "stream<%s,dh%d,q%d,c%d>", dn, DH, z.q, z.c);
+    return;
+  }
+  const MhaBwdPick p = mha_bwd_pick<DH>(T, dtype);
+  switch (p.kind) {
+    case MHA_BWD_ONEPASS: snprintf(out, len, "mha_bwd1_bf16_kernel<%d>", DH); return;
+    case MHA_BWD_ONEPASS_640: snprintf(out, len, "mha_bwd1_bf16_kernel<%d,640>", DH); return;
+    case MHA_BWD_TWOPHASE: snprintf(out, len, "mha_bwd_bf16_kernel<%d>", DH); return;
+    case MHA_BWD_F32: snprintf(out, len, "mha_bwd_f32_kernel<%d>", DH); return;
+    default: break;
+  }
+  const MhaStreamSizes z = mha_stream_sizes(dtype, 1);
+  snprintf(out, len, "stream<%s,dh%d,q%d,k%d,c%d>", dn, DH, z.q, z.k, z.c);
+}
+
+extern "C" int tmae_mha_plan(int T, int dh, int dtype, int backward, char* out, int len) {
+  TMAE_REQUIRE(out != nullptr && len > 0 && T >= 0, "tmae_mha_plan: bad arguments");
+  TMAE_REQUIRE(dh == 32 || dh == 64 || dh == 80, "tmae_mha_plan: head dim %d unsupported (32, 64 or 80)", dh);
+  TMAE_REQUIRE(dtype == TMAE_BF16 || dtype == TMAE_F32, "tmae_mha_plan: dtype %d unsupported", dtype);
+  if (dh == 80) mha_plan_t<80>(T, dtype, backward, out, len);
+  else if (dh == 64) mha_plan_t<64>(T, dtype, backward, out, len);
+  else mha_plan_t<32>(T, dtype, backward, out, len);
+  return TMAE_OK;
+}
+
+extern "C" int tmae_mha_force_stream(int on) {
+  const int prev = g_tmae_mha_force_stream;
+  g_tmae_mha_force_stream = on ? 1 : 0;
+  return prev;
 }

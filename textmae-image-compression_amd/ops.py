@@ -18,7 +18,7 @@ from ._lib import ACT_GELU, ACT_NONE, TMAE_BF16, TMAE_F32, ConvArgs, EBParams, L
 __all__ = [
     "ids_shuffle", "layernorm", "linear", "linear_residual", "patch_embed", "cls_rows", "mha", "decoder_embed",
     "mask_rows", "decoder_pred", "conv3x3", "lic_stack", "pack_lic_stack_weight", "lic_stack_fits", "gc_slices", "eb_likelihood", "eb_aux_loss",
-    "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "dtype_code", "gc_slices_code", "gc_indexes",
+    "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "mha_plan", "mha_force_stream", "dtype_code", "gc_slices_code", "gc_indexes",
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "rans_encode_lanes", "rans_decode_lanes",
@@ -77,6 +77,26 @@ def force_gemm_tile(index: int):
         yield
     finally:
         _lib.value("tmae_gemm_force_tile", prev)
+
+
+def mha_plan(T: int, dh: int, dtype: torch.dtype, backward: bool = False) -> str:
+    """name of the attention kernel family tmae_mha_fwd / tmae_mha_fwd_lse (or tmae_mha_bwd) launches at this
+    sequence length, with the streamed family's block and chunk sizes, e.g. "stream<bf16,dh64,q256,c128>"
+    (no device work)"""
+    buf = ctypes.create_string_buffer(96)
+    _lib.call("tmae_mha_plan", T, dh, dtype_code(dtype), int(bool(backward)), buf, len(buf))
+    return buf.value.decode()
+
+
+@contextlib.contextmanager
+def mha_force_stream(on: bool = True):
+    """Test hook: every attention launch inside the block takes the streamed kernels (tmae_mha_force_stream),
+    whatever the sequence length.  The previous value is restored on exit."""
+    prev = _lib.value("tmae_mha_force_stream", int(bool(on)))
+    try:
+        yield
+    finally:
+        _lib.value("tmae_mha_force_stream", prev)
 
 
 # --------------------------------------------------------------------------------------- masking

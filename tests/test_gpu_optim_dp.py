@@ -558,6 +558,38 @@ def test_graphed_train_step_bitwise(dt):
         assert torch.equal(m1(imgs, scores)["x_hat"], m2(imgs, scores)["x_hat"])
 
 
+def test_eager_step_after_graphed_steps_bitwise():
+    """an eager engine.train_step on a model that has trained through GraphedTrainStep (a warm-up step, the capture,
+    two replays) equals the same batches as eager steps only: losses and post-step weights bit for bit.  The eager
+    backward runs a slice's mean and scale stacks on two streams as one-problem launches, the captured one as a
+    2-problem launch: both take their transposed fragment-order weights from the one pack of the pair, so the
+    eager step after the replays reads re-laid-out weights (a cache holding both groupings refreshed only one)"""
+    from textmae_amd import engine
+    from textmae_amd.optim import configure_optimizers
+    from textmae_amd.rd_loss import RateDistortionLoss
+
+    crit = RateDistortionLoss(lmbda=1e-2)
+    m1, cfg = _model(SMALL, 27, torch.bfloat16)
+    m2, _ = _model(SMALL, 27, torch.bfloat16)
+    m1.distortion = m2.distortion = "ssim+l1"
+    batches = [_inputs(cfg, 2, 900 + i) for i in range(4)]
+    o1 = configure_optimizers(m1, lr=3e-3, aux_lr=1e-3, fused=True)
+    o2 = configure_optimizers(m2, lr=3e-3, aux_lr=1e-3, fused=True)
+    cu = lambda b: tuple(t.cuda() for t in b)  # noqa: E731
+    imgs, scores, zn, yn = cu(batches[0])
+    g = engine.GraphedTrainStep(m1, crit, *o1, imgs, scores, clip_max_norm=1.0, warmup=1, noise=(zn, yn))
+    la = []
+    for b in batches[1:3]:
+        imgs, scores, zn, yn = cu(b)
+        la.append(float(g(imgs, scores, noise=(zn, yn))["loss"]))
+    la += _train_steps(m1, *o1, batches[3:], crit)  # the eager step after the replays
+    assert m1._train_exec._fused_bwd  # the fused chain ran (its "licT" packs are the ones at stake)
+    lb = _train_steps(m2, *o2, batches, crit)[1:]
+    assert la == lb, (la, lb)
+    for (n, p), q in zip(m1.named_parameters(), m2.parameters()):
+        assert torch.equal(p, q), n
+
+
 def test_graphed_train_step_lr_change_before_first_replay():
     """a learning-rate change BEFORE the first replay re-captures at once: the launch tables the first capture
     built (relayout, Adam) were never filled (their copy nodes had not run), so the second capture and an eager

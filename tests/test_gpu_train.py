@@ -467,6 +467,35 @@ def test_mcm_train_grads_f32_vs_oracle():
     assert not bad, bad[:20]
 
 
+TWO_SLICES = dict(SMALL, num_slices=2, latent_depth=32)
+
+
+def test_mcm_train_two_slices_f32_vs_oracle():
+    """num_slices = 2: one slice follows the support slices, so it runs as a serial slice too (TrainExec.nser = S)
+    -- slice 1 reads support slot 0 and writes none, and no slice group is batched.  Same metric and bounds as
+    test_mcm_train_grads_f32_vs_oracle"""
+    m, cfg, sd, imgs, scores, zn, yn, R = _model_and_oracle(TWO_SLICES, 6, 2, torch.float32)
+    hip, out, loss, aux = _hip_grads(m, imgs, scores, zn, yn, R)
+    assert m._train_exec.nser == 2 and not m._train_exec._fused_ok()
+    ref, x_ref, loss_ref, aux_ref = _oracle_grads(cfg, sd, imgs, scores, zn, yn, R)
+    check("_rel:out_x_hat_two_slices", _rel(out["x_hat"], x_ref), 1e-4)
+    assert abs(loss.item() - loss_ref.item()) < 1e-4 * max(1.0, abs(loss_ref.item()))
+    assert abs(aux.item() - aux_ref.item()) < 1e-4 * abs(aux_ref.item())
+    bad, worst = [], 0.0
+    for name, g in hip.items():
+        r = ref[name].float()
+        if r.abs().max() == 0:
+            if g.abs().max() > 1e-6:
+                bad.append((name, "nonzero", g.abs().max().item()))
+            continue
+        e = _rel(g, r)
+        worst = max(worst, e)
+        if e > 2e-3:
+            bad.append((name, e))
+    check("grad_maxrel_worst_tensor_two_slices_f32", worst, 2e-3, strict=False, tensors=len(hip))
+    assert not bad, bad[:20]
+
+
 def test_mcm_train_bf16_close_to_f32():
     m, cfg, sd, imgs, scores, zn, yn, R = _model_and_oracle(SMALL, 4, 2, torch.float32)
     g32, *_ = _hip_grads(m, imgs, scores, zn, yn, R)
@@ -509,7 +538,7 @@ def test_train_fused_stacks_vs_per_layer(geom):
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_side_stream_wgrads_bitwise(dt):
-    """weight gradients on the side stream (mcm_train._wg, deferred one-per-group forks) == the same backward
+    """weight gradients on the side stream (_VitTrainBase._wg, deferred one-per-group forks) == the same backward
     with every weight gradient on the compute stream, bit for bit; and the side stream really ran them"""
     m, cfg, sd, imgs, scores, zn, yn, R = _model_and_oracle(SMALL, 5, 3, dt)
     g_side, *_ = _hip_grads(m, imgs, scores, zn, yn, R)
@@ -637,7 +666,7 @@ def test_relayout_multi_dense_and_strided(T, dt):
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_weight_cache_refresh_modes(dt):
-    """mcm_train._Weights: the lazy first build and the one-launch refresh (tmae_relayout_multi modes: plain
+    """train_weights._Weights: the lazy first build and the one-launch refresh (tmae_relayout_multi modes: plain
     cast, 64 x 64 LDS transposes for W^T and the conv data-gradient layout, per-row [Cin][9] -> [9][Cin] for conv
     weights) equal torch's layouts exactly, including ragged transpose edges"""
     from textmae_amd.mcm_train import _Weights

@@ -8,7 +8,7 @@ one flat f32 buffer whose views autograd adopts as ``p.grad``:
 
   forward_loss (198-214)         tmae_mae_loss_bwd: mask * 2 (pred - target) / (p*p*c * sum(mask)), norm_pix targets
   decoder_pred / decoder_norm    split-K TN weight gradient, transposed-weight data gradient, LayerNorm backward
-  decoder blocks                 the timm Block backward shared with MCM (_VitTrainBase._block_bwd)
+  decoder blocks                 the timm Block backward shared with MCM (vit_train._VitTrainBase._block_bwd)
   decoder_embed + mask_token     unshuffle gather of the token gradients (172-190: the cls row stays first), the
                                  mask-token gradient summed over the masked positions
   norm, encoder blocks           LayerNorm over every token (cls included), Block backward
@@ -21,7 +21,8 @@ import torch
 
 from . import ops
 from . import train_ops as T
-from .mcm_train import _SIDE_SLOT_DIV, _VitTrainBase, _Weights, _block_params
+from .train_weights import _Weights
+from .vit_train import _SIDE_SLOT_DIV, _VitTrainBase, _block_params
 
 
 class MAETrainExec(_VitTrainBase):

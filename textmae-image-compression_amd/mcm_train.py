@@ -15,480 +15,24 @@ Reference semantics reproduced (compressai 1.2.4 / timm 0.4.5 restated, SURVEY Â
   * LowerBound backward (gradient passes where x >= bound or grad < 0);
   * the main loss's gradient on ``*.quantiles`` is exactly zero (d z_hat / d median = -1 + 1) and is
     returned as zeros, so clip_grad_norm_ / aux_loss.backward() see what they see in the reference.
-The slice loop runs slice by slice (no batching of slices 6-11 in training).
+The slice loop runs slices 0..ms-1 one by one and slices ms..S-1, which condition on the same support slots, as one
+group (TrainExec._group_fwd / _slices_bwd).  The weight cache is train_weights._Weights, the machinery shared with
+the MAE executor vit_train._VitTrainBase.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
 from . import train_ops as T
 from .ops import ACT_GELU, ACT_NONE
-from .optim import device_table, table_usable
-
-
-# side-stream weight gradients size their split-K for half the chip's CU slots (the data-gradient chain holds the
-# rest): graphed step 31.49 -> 31.24 ms; a quarter made the side stream the critical path (40.2 ms)
-_SIDE_SLOT_DIV = 2
+from .train_weights import _Weights  # noqa: F401  (re-exported: tests and tools import it from here)
+from .vit_train import _SIDE_SLOT_DIV, _bias, _BlockSaved, _block_params, _VitTrainBase  # noqa: F401
 
 
 def _convs(seq):
     return [l for l in seq if isinstance(l, nn.Conv2d)]
-
-
-class _Weights:
-    """Kernel-layout copies of the f32 parameters, rebuilt when a parameter's version changes (once per
-    optimizer step).  The first build of each (parameter, layout) is lazy; afterwards ``refresh()`` re-lays
-    out every stale copy in ONE multi-tensor launch (tmae_relayout_multi): plain casts as vectors, 2-D
-    transposes (W^T, the conv data-gradient layout) as 64 x 64 LDS tiles, conv weights [Cout][Cin][3][3] ->
-    [Cout][3][3][Cin] one row per block through LDS."""
-
-    def __init__(self, dtype):
-        self.dtype = dtype
-        self.cache = {}   # (id(p), kind) -> [sig, tensor, p, job]; job = (dims, strides) or None (a view)
-        self.packs = {}   # (param ids, kind) -> packed buffer whose rows are those params' cache entries
-        self._tab = None
-
-    def _get(self, p, kind, make):
-        key = (id(p), kind)
-        sig = (p.data_ptr(), p._version)
-        hit = self.cache.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        w = p.detach()
-        if hit is not None and hit[3] is not None and hit[0] is not None and hit[0][0] == sig[0]:
-            dst, job = hit[1], hit[3]  # same parameter storage, newer values: re-lay out in place (keeps packing)
-        elif hit is not None and hit[0] is None:
-            dst, job = hit[1], hit[3]  # a packed row registered by packed(), first build
-        else:
-            dst, job = make(w)
-        if job is not None:
-            if job[0] == "lic":  # first build of a fragment-order pack (later ones: relayout_multi mode 3)
-                _, co, ci, lo, n = job
-                dst.copy_(ops.pack_lic_stack_weight(w[:, lo:lo + n], self.dtype))
-            elif job[0] == "licT":  # the transposed, tap-flipped pack (relayout mode 4)
-                dst.copy_(ops.pack_lic_stack_weight_t(w, self.dtype))
-            else:
-                T.relayout(w, dst, *job)
-        self.cache[key] = [sig, dst, p, job]
-        return dst
-
-    def packed(self, params, kind):
-        """one buffer holding the `kind` layouts ("conv", "conv_dg" or "bias") of `params` back to back, so a batched
-        launch reaches problem j at a constant stride; each row is also that parameter's cache entry"""
-        key = (tuple(id(p) for p in params), kind)
-        buf = self.packs.get(key)
-        if buf is None:
-            p0 = params[0]
-            if kind == "conv":
-                co, ci = p0.shape[:2]
-                buf = torch.empty((len(params), co, 9 * ci), dtype=self.dtype, device=p0.device)
-                job = ((co, 3, 3, ci), (ci * 9, 3, 1, 9))
-            elif kind == "conv_dg":  # the transposed-conv data-gradient layout of conv_dg(), problems back to back
-                co, ci = p0.shape[:2]
-                buf = torch.empty((len(params), ci, 9 * co), dtype=self.dtype, device=p0.device)
-                job = ((ci * 9, 1, 1, co), (1, 0, 0, ci * 9))
-            elif isinstance(kind, tuple) and kind[0] == "lic":  # ("lic", lo, n): input channels [lo, lo + n) packed
-                co = p0.shape[0]
-                lo, n = kind[1], kind[2]
-                total = 9 * (-(-n // 32)) * (-(-co // 16)) * 512
-                buf = torch.empty((len(params), total), dtype=self.dtype, device=p0.device)
-                for j, p in enumerate(params):
-                    self.cache[(id(p), kind)] = [None, buf[j], p, ("lic", co, p.shape[1], lo, n)]
-                self.packs[key] = buf
-                for p in params:
-                    self._get(p, kind, None)
-                return buf
-            elif kind == "licT":  # the transposed conv's weight in fragment order (the fused stack backward)
-                co, ci = p0.shape[:2]
-                total = 9 * (-(-co // 32)) * (-(-ci // 16)) * 512
-                buf = torch.empty((len(params), total), dtype=self.dtype, device=p0.device)
-                for j, p in enumerate(params):
-                    self.cache[(id(p), kind)] = [None, buf[j], p, ("licT", co, ci)]
-                self.packs[key] = buf
-                for p in params:
-                    self._get(p, kind, None)
-                return buf
-            elif isinstance(kind, tuple) and kind[0] == "conv_lat":  # ("conv_lat", n): input channels [0, n), conv layout
-                co, n = p0.shape[0], kind[1]
-                buf = torch.empty((len(params), co, 9 * n), dtype=self.dtype, device=p0.device)
-                for j, p in enumerate(params):
-                    ci = p.shape[1]
-                    self.cache[(id(p), kind)] = [None, buf[j], p, ((co, 3, 3, n), (ci * 9, 3, 1, 9))]
-                self.packs[key] = buf
-                for p in params:
-                    self._get(p, kind, None)
-                return buf
-            else:
-                buf = torch.empty((len(params), p0.numel()), dtype=torch.float32, device=p0.device)
-                job = ((p0.numel(),), (1,))
-            for j, p in enumerate(params):
-                self.cache[(id(p), kind)] = [None, buf[j], p, job]
-            self.packs[key] = buf
-        for p in params:
-            self._get(p, kind, None)
-        return buf
-
-    @staticmethod
-    def _is_transpose(dims, strides):
-        d = list(dims) + [1] * (4 - len(dims))
-        st = list(strides) + [0] * (4 - len(strides))
-        return d[1] == 1 and d[2] == 1 and st[0] == 1 and st[3] >= d[0]
-
-    def refresh(self):
-        """re-lay out every cached copy whose parameter moved since it was built"""
-        stale = [e for e in self.cache.values() if e[0] != (e[2].data_ptr(), e[2]._version)]
-        if not stale:
-            return
-        rows, chunk, ptrs = [], 0, []
-        # a parameter whose plain cast and transpose are both stale: the transpose row writes the cast too (mode 1
-        # with a second destination), so the f32 weight is read once
-        casts = {id(e[2]): e for e in stale if e[3] is not None and e[3][0] != "lic" and e[3][0] != "licT"
-                 and tuple(e[3][0]) == (e[2].numel(),) and tuple(e[3][1]) == (1,)}
-        fused = {}
-        for e in stale:
-            job = e[3]
-            if job is None or job[0] in ("lic", "licT") or id(e[2]) not in casts:
-                continue
-            d = list(job[0]) + [1] * (4 - len(job[0]))
-            st = list(job[1]) + [0] * (4 - len(job[1]))
-            # the transpose of the parameter's own contiguous [R][C] storage
-            if self._is_transpose(job[0], job[1]) and st[3] * d[3] == e[2].numel() and st[3] == d[0]:
-                fused[id(e[2])] = (e, casts[id(e[2])])
-        skip = {id(c) for _, c in fused.values()}
-        for e in stale:
-            sig, dst, p, job = e
-            e[0] = (p.data_ptr(), p._version)
-            if job is None or id(e) in skip:
-                continue
-            if job[0] == "licT":  # the transposed fragment order (relayout mode 4)
-                _, co, ci = job
-                total = 9 * (-(-co // 32)) * (-(-ci // 16)) * 512
-                rows.append([p.data_ptr(), dst.data_ptr(), ops.dtype_code(dst.dtype) | (4 << 8), co, ci, 0, 0, 0, 0, 0,
-                             total, chunk])
-                ptrs.append((p.data_ptr(), dst.data_ptr()))
-                chunk += -(-(total // 72) // 256)  # 256 units of 9 taps x 8 elements per chunk
-                continue
-            if job[0] == "lic":  # tmae_lic_stack fragment order (relayout mode 3)
-                _, co, ci, lo, n = job
-                total = 9 * (-(-n // 32)) * (-(-co // 16)) * 512
-                rows.append([p.data_ptr(), dst.data_ptr(), ops.dtype_code(dst.dtype) | (3 << 8), co, ci, lo, n, 0, 0, 0,
-                             total, chunk])
-                ptrs.append((p.data_ptr(), dst.data_ptr()))
-                chunk += -(-(total // 72) // 256)
-                continue
-            dims, strides = job
-            d = list(dims) + [1] * (4 - len(dims))
-            st = list(strides) + [0] * (4 - len(strides))
-            total = d[0] * d[1] * d[2] * d[3]
-            if total >= 1 << 31:
-                raise ValueError(f"weight relayout of {total} elements exceeds the 32-bit index range")
-            if self._is_transpose(dims, strides):  # dst [C][R] of src [R][C] (C = d0, R = d3, ld = s3)
-                mode, n = 1, -(-d[3] // 64) * -(-d[0] // 64)
-                st[1] = 0  # mode 1 reads s1 as the second destination (none unless fused below)
-                f = fused.get(id(p))
-                if f is not None and f[0] is e:  # + the plain cast into the "nt" copy (s1 = its address)
-                    if f[1][1].dtype != dst.dtype:
-                        raise ValueError("relayout: a fused cast copy must have the transpose's dtype")
-                    st[1] = f[1][1].data_ptr()
-                    ptrs.append((p.data_ptr(), st[1]))
-            elif (d[1] * d[2] * d[3] <= 8192 and st[2] == 1 and st[1] == d[2] and st[3] == d[1] * d[2]
-                  and st[0] == d[1] * d[2] * d[3]):  # per-row [A][B] -> [B][A]
-                mode, n = 2, d[0]
-            else:
-                mode, n = 0, (total + 32767) // 32768
-            rows.append([p.data_ptr(), dst.data_ptr(), ops.dtype_code(dst.dtype) | (mode << 8), d[1], d[2], d[3], *st,
-                         total, chunk])
-            ptrs.append((p.data_ptr(), dst.data_ptr()))
-            chunk += n
-        if not rows:
-            return
-        key = tuple(ptrs)
-        if self._tab is None or self._tab[0] != key or not table_usable(self._tab[3]):
-            dev = stale[0][1].device
-            owner = [t for t in range(len(rows)) for _ in range(rows[t + 1][11] - rows[t][11] if t + 1 < len(rows)
-                                                                else chunk - rows[t][11])]
-            flat = [v for r in rows for v in r] + owner  # the rows, then each chunk's row (tmae.h)
-            tab, epoch = device_table(flat, dev)
-            self._tab = (key, tab, chunk, epoch)
-        _lib.call("tmae_relayout_multi", self._tab[1].data_ptr(), len(rows), self._tab[2],
-                  torch.cuda.current_stream().cuda_stream)
-
-    def _cast_same(self, w2):
-        if self.dtype == torch.float32:
-            return w2.contiguous(), None
-        return torch.empty(w2.shape, dtype=self.dtype, device=w2.device), ((w2.numel(),), (1,))
-
-    def nt(self, p, rows=None):
-        """nn.Linear / 1x1 conv weight as [N][K] in the operand dtype"""
-        return self._get(p, "nt", lambda w: self._cast_same(w.reshape(w.shape[0], -1) if rows is None
-                                                            else w.reshape(rows, -1)))
-
-    def t(self, p, rows=None):
-        """transposed [K][N] (the data-gradient operand of y = x W^T)"""
-        def b(w):
-            w2 = w.reshape(w.shape[0], -1) if rows is None else w.reshape(rows, -1)
-            N, K = w2.shape
-            return torch.empty((K, N), dtype=self.dtype, device=w.device), ((K, 1, 1, N), (1, 0, 0, K))
-        return self._get(p, "t", b)
-
-    def raw(self, p):
-        """the weight as stored ([cin][cout] for ConvTranspose2d 1x1), cast"""
-        return self._get(p, "raw", lambda w: self._cast_same(w.reshape(w.shape[0], -1)))
-
-    def conv(self, p):
-        """Conv2d 3x3 weight [Cout][Cin][3][3] -> [Cout][3][3][Cin] (forward implicit GEMM)"""
-        def b(w):
-            co, ci = w.shape[:2]
-            return torch.empty((co, 9 * ci), dtype=self.dtype, device=w.device), ((co, 3, 3, ci), (ci * 9, 3, 1, 9))
-        return self._get(p, "conv", b)
-
-    def conv_dg(self, p):
-        """-> [Cin][3][3][Cout] (transposed-conv data gradient)"""
-        def b(w):
-            co, ci = w.shape[:2]
-            # dst[ci][tap][co] = w[co][ci][tap]: the transpose of w seen as [Cout][Cin * 9]
-            return torch.empty((ci, 9 * co), dtype=self.dtype, device=w.device), ((ci * 9, 1, 1, co), (1, 0, 0, ci * 9))
-        return self._get(p, "conv_dg", b)
-
-
-class _BlockSaved:
-    __slots__ = ("x", "a1", "qkv", "att", "lse", "xmid", "a2", "hpre", "h")
-
-
-class _VitTrainBase:
-    """What the MCM and MAE training executors share: workspaces, the flat gradient buffer laid out in the order
-    the backward finishes the parameters (DP buckets), and the timm Block forward (keeping what its backward
-    needs) / backward."""
-
-    _side = None          # side stream of the weight gradients (_wg), made by _side_begin
-    # split-K of the ViT blocks' weight gradients sized for 1 / VIT_WG_SLOT_DIV of the CU slots (test / A-B hook;
-    # the side stream shares the chip with the data-gradient chain)
-    VIT_WG_SLOT_DIV = _SIDE_SLOT_DIV
-    SIDE_SLOT_DIV = _SIDE_SLOT_DIV  # the other side-stream weight gradients' (LIC convs) split-K slot divisor
-    _side_used = False
-    _pending = ()
-    _queued = ()
-    _groups = ()
-
-    def _layout(self):
-        """parameter gradient layout: the order in which the backward finishes them (DP buckets)"""
-        self.params = [p for p in self._grad_order() if p.requires_grad]
-        self.offsets = {}
-        off = 0
-        for p in self.params:
-            self.offsets[id(p)] = off
-            off += p.numel()
-        self.numel = off
-        self._gflat = None
-
-    # ------------------------------------------------------------------ helpers
-    def _e(self, *shape, dtype=None):
-        return torch.empty(shape, dtype=dtype or self.dtype, device=self.device)
-
-    def _z(self, *shape, dtype=torch.float32):
-        return torch.zeros(shape, dtype=dtype, device=self.device)
-
-    def _cast(self, src):
-        """f32 -> operand dtype (identity for the f32 path)"""
-        if self.dtype == torch.float32:
-            return src
-        return T.relayout(src, torch.empty(src.shape, dtype=self.dtype, device=self.device), (src.numel(),), (1,))
-
-    def grads_buffer(self, fresh):
-        if fresh or self._gflat is None:
-            buf = torch.empty(self.numel, dtype=torch.float32, device=self.device)
-            if fresh:
-                return buf
-            self._gflat = buf
-        return self._gflat
-
-    def grad(self, p):
-        off = self.offsets[id(p)]
-        return self.gflat[off:off + p.numel()].view(p.shape)
-
-    def _ready(self, p):
-        """every gradient up to and including p's is final (DP bucket hand-off).  With weight gradients on the
-        side stream the hand-off lags one call: the compute stream waits for the side stream's work up to the
-        PREVIOUS hand-off point and issues that bucket's collective.
-        Round 6 (profiles/r06/c2_*, c5-c7): in a captured one-rank DP step these waits are what costs the +4 ms
-        over the plain graphed step (31.8-32.9 vs 27.8-28.6 ms): the side stream runs far behind the data-gradient
-        chain, so the chain stalls at some hand-offs (a kernel trace: 24 HIP-queue hops of the compute chain, 3.75 ms
-        of gaps at them, the largest 1.76 ms), and RCCL's one-rank reduce kernels (32 workgroups, ~110 us per 64 MB
-        bucket) share the chip with the backward.  Issuing each collective from the side stream instead (it then
-        waits for the compute stream's hand-off point, the compute stream never waits inside the backward), or from a
-        third stream joined to both, measured 36.7-37.6 ms; a lag of 2 / 4 hand-offs 31.8 / 33.2 ms; HIP graph
-        queue counts (DEBUG_HIP_FORCE_GRAPH_QUEUES 2 / 3) changed nothing."""
-        if self.sync is None:
-            self._wg_flush()
-            return
-        if self._side is not None:
-            self._wg_flush(last=True)  # the event below must follow every group up to p
-        upto = self.offsets[id(p)] + p.numel()
-        if not self._side_used:
-            self.sync.ready(upto)
-            return
-        ev = torch.cuda.Event()
-        ev.record(self._side)
-        self._pending.append((ev, upto))
-        main = torch.cuda.current_stream(self.device)
-        while len(self._pending) > 1:
-            e, u = self._pending.pop(0)
-            main.wait_event(e)
-            self.sync.ready(u)
-
-    # ------------------------------------------------------------------ side-stream weight gradients
-    def _side_begin(self):
-        """called at the top of a backward: a side stream for the weight gradients when on a GPU"""
-        if "_side" not in self.__dict__:  # the class default is None
-            self._side = torch.cuda.Stream(device=self.device) if torch.device(self.device).type == "cuda" else None
-        self._side_used = False
-        self._side_calls = 0  # weight gradients the side stream ran in this backward (tests)
-        self._pending, self._keep, self._queued, self._groups = [], [], [], []
-
-    TIMING_SKIP_WG = False  # diagnostics: drop every queued weight gradient (wrong gradients; timing A/B only)
-
-    def _wg(self, a, *args, **kw):
-        """T.wgrad for the side stream: a weight gradient has no consumer inside the backward, so it runs under
-        the serial data-gradient chain.  Queued here and enqueued by _wg_flush behind ONE fork per group (a stack,
-        a block): a captured graph pays a cross-queue dependency per fork.  `a` (this layer's output gradient, a
-        fresh tensor of the chain) is kept alive until the join; every other operand is a saved activation."""
-        if self.TIMING_SKIP_WG:  # timing diagnostics only (tools/train_ab.py): the step without weight gradients
-            return
-        if self._side is None:  # same split plan as the side stream's, so both modes sum in the same order
-            kw.setdefault("slot_div", self.SIDE_SLOT_DIV)
-            return T.wgrad(a, *args, **kw)
-        self._queued.append((a, args, kw))
-
-    def _wg_many(self, items, M, N, K, dt, conv=None, **kw):
-        """the weight gradients of several problems of one shape (the same layer of several slices' stacks): ONE
-        batched launch (tmae_wgrad_args.nb) when every operand and output sits at a constant element stride from
-        the previous problem's, else one launch each.  items: dicts a (output gradient), b (layer input), out / bias
-        (the parameter's gradient views), x2 (conv second input pointer or None)."""
-        P = len(items)
-
-        def ptr(v):
-            return v if isinstance(v, int) else v.data_ptr()
-
-        def stride(key, esz):
-            vals = [it.get(key) for it in items]
-            if vals[0] is None:
-                return 0 if all(v is None for v in vals) else None
-            d = {ptr(b) - ptr(a) for a, b in zip(vals, vals[1:])}
-            if P == 1:
-                return 0
-            if len(d) != 1 or next(iter(d)) % esz:
-                return None
-            return next(iter(d)) // esz
-
-        eb = items[0]["b"].element_size()
-        st = [stride("a", items[0]["a"].element_size()), stride("b", eb), stride("x2", eb), stride("out", 4),
-              stride("bias", 4)]
-        if P > 1 and None not in st:
-            # the launch reads problems 1.. through pointer strides: keep their output gradients (fresh tensors of the
-            # chain, unlike the saved activations) alive until the join, as _wg_flush does for the first one's
-            self._keep.extend(it["a"] for it in items[1:] if not isinstance(it["a"], int))
-            it = items[0]
-            cv = dict(conv, x2=it.get("x2")) if conv is not None else None
-            self._wg(it["a"], it["b"], M, N, K, it["out"], dt, bias=it.get("bias"), conv=cv, batch=(P, *st), **kw)
-            return
-        for it in items:
-            cv = dict(conv, x2=it.get("x2")) if conv is not None else None
-            self._wg(it["a"], it["b"], M, N, K, it["out"], dt, bias=it.get("bias"), conv=cv, **kw)
-
-    def _wg_flush(self, last=False):
-        """close the queued group: record its fork point on the compute stream now, but enqueue the group on the
-        side stream only at the NEXT flush (or the join), after the compute stream's next kernels -- in a captured
-        graph the fork node's first child is then the compute chain's next kernel, which keeps the compute
-        chain on its own queue (the side branch takes the cross-queue dependency instead)"""
-        if self._queued:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            self._groups.append((ev, self._queued))
-            self._queued = []
-        while len(self._groups) > (0 if last else 1):
-            ev, group = self._groups.pop(0)
-            self._side.wait_event(ev)
-            with torch.cuda.stream(self._side):
-                for a, args, kw in group:
-                    kw.setdefault("slot_div", self.SIDE_SLOT_DIV)
-                    T.wgrad(a, *args, ws_slot=4, **kw)
-                    self._keep.append(a)
-                    self._side_calls += 1
-            self._side_used = True
-
-    def _side_join(self):
-        """order the compute stream after every side-stream weight gradient and hand off what is left"""
-        if self._side is not None:
-            self._wg_flush(last=True)
-        if self._side is not None and self._side_used:
-            torch.cuda.current_stream(self.device).wait_stream(self._side)
-            for _, u in self._pending:
-                self.sync.ready(u)
-        self._pending, self._keep, self._side_used = [], [], False
-
-    def _block_fwd(self, blk, x, B, Tn, store=None):
-        dt, W = self.dtype, self.w
-        rows, D = x.shape
-        s = _BlockSaved()
-        s.x = x
-        s.a1 = ops.layernorm(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt)
-        s.qkv = ops.linear(s.a1, W.nt(blk.attn.qkv.weight), _bias(blk.attn.qkv.bias), dt)
-        H = blk.attn.num_heads
-        s.att = self._e(rows, D)
-        s.lse = torch.empty((B * H * Tn,), dtype=torch.float32, device=self.device)
-        T.mha_lse(s.qkv, B, Tn, H, D // H, blk.attn.scale, dt, s.att, s.lse)
-        s.xmid = torch.empty_like(x)
-        T.linear_residual_out(s.att, W.nt(blk.attn.proj.weight), _bias(blk.attn.proj.bias), x, s.xmid, dt)
-        s.a2 = ops.layernorm(s.xmid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt)
-        hid = blk.mlp.fc1.out_features
-        s.h, s.hpre = self._e(rows, hid), self._e(rows, hid)
-        T.linear_pre(s.a2, W.nt(blk.mlp.fc1.weight), _bias(blk.mlp.fc1.bias), dt, ACT_GELU, s.h, s.hpre)
-        out = torch.empty_like(x)
-        T.linear_residual_out(s.h, W.nt(blk.mlp.fc2.weight), _bias(blk.mlp.fc2.bias), s.xmid, out, dt)
-        (self.enc if store is None else store).append(s)
-        return out
-
-    def _block_bwd(self, blk, s, dres, dres_op, B, Tn):
-        """timm Block backward: (dres f32, dres in the operand dtype) -> the same for the block input"""
-        dt, W, G = self.dtype, self.w, self.grad
-        rows, D = dres.shape
-        hid = blk.mlp.fc1.out_features
-        H = blk.attn.num_heads
-        f32 = dt == torch.float32
-        # fc2 (+ GELU of fc1 in the data-gradient epilogue)
-        sd = self.VIT_WG_SLOT_DIV
-        self._wg(dres_op, s.h, D, hid, rows, G(blk.mlp.fc2.weight), dt, slot_div=sd)  # fc2.bias: in norm2's backward
-        dh = self._e(rows, hid)
-        T.dgrad_linear(dres_op, W.t(blk.mlp.fc2.weight), rows, D, hid, dt, out=dh, pre=s.hpre)
-        # fc1
-        self._wg(dh, s.a2, hid, D, rows, G(blk.mlp.fc1.weight), dt, bias=G(blk.mlp.fc1.bias), slot_div=sd)
-        da2 = torch.empty((rows, D), dtype=torch.float32, device=self.device)
-        T.dgrad_linear(dh, W.t(blk.mlp.fc1.weight), rows, hid, D, dt, out=da2)
-        # norm2 + residual
-        dmid = torch.empty((rows, D), dtype=torch.float32, device=self.device)
-        dmid_op = dmid if f32 else self._e(rows, D)
-        T.layernorm_bwd(s.xmid, blk.norm2.weight, da2, dmid, rows, D, blk.norm2.eps, G(blk.norm2.weight),
-                        G(blk.norm2.bias), dres=dres, dxop=None if f32 else dmid_op, dres_colsum=G(blk.mlp.fc2.bias))
-        # proj
-        self._wg(dmid_op, s.att, D, D, rows, G(blk.attn.proj.weight), dt, slot_div=sd)  # proj.bias: in norm1's bwd
-        datt = self._e(rows, D)
-        T.dgrad_linear(dmid_op, W.t(blk.attn.proj.weight), rows, D, D, dt, out=datt)
-        # attention core
-        dqkv = self._e(rows, 3 * D)
-        T.mha_bwd(s.qkv, s.att, datt, s.lse, dqkv, B, Tn, H, D // H, blk.attn.scale, dt)
-        # qkv
-        self._wg(dqkv, s.a1, 3 * D, D, rows, G(blk.attn.qkv.weight), dt,
-                 bias=G(blk.attn.qkv.bias) if blk.attn.qkv.bias is not None else None, slot_div=sd)
-        da1 = torch.empty((rows, D), dtype=torch.float32, device=self.device)
-        T.dgrad_linear(dqkv, W.t(blk.attn.qkv.weight), rows, 3 * D, D, dt, out=da1)
-        # norm1 + residual
-        dx = torch.empty((rows, D), dtype=torch.float32, device=self.device)
-        dx_op = dx if f32 else self._e(rows, D)
-        T.layernorm_bwd(s.x, blk.norm1.weight, da1, dx, rows, D, blk.norm1.eps, G(blk.norm1.weight),
-                        G(blk.norm1.bias), dres=dmid, dxop=None if f32 else dx_op, dres_colsum=G(blk.attn.proj.bias))
-        return dx, dx_op
 
 
 class TrainExec(_VitTrainBase):
@@ -511,6 +55,22 @@ class TrainExec(_VitTrainBase):
         self.sw = m.latent_depth // m.num_slices
         self.ms = m.num_slices // 2
         self.mid = [l.out_channels for l in _convs(m.cc_transform_mean[0])]
+        S, ms = m.num_slices, self.ms
+        self.cm, self.cs, self.cl = ([_convs(seq[i]) for i in range(S)]
+                                     for seq in (m.cc_transform_mean, m.cc_transform_scale, m.lrp_transform))
+        # slices 0..nser-1 run one by one (each conditions on the ones before); slices ms..S-1 all condition on y_hat
+        # slots 0..ms-1 only (max_support_slices, MCM.py:73, 756-758), so two or more of them run as one group
+        self.nser = ms if S - ms > 1 else S
+        # launch groups: the [mean.. | scale..] stacks and the lrp stacks of each slice group.  A stack's weight packs
+        # are always its launch group's (_pack), whichever launch asks and on however many streams: the weight cache
+        # keeps one grouping per parameter
+        self._lgroup = {}
+        self.slice_groups = [(i, 1) for i in range(self.nser)] + ([(self.nser, S - self.nser)] if self.nser < S else [])
+        for i0, nbs in self.slice_groups:
+            sl = range(i0, i0 + nbs)
+            for grp in ([self.cm[i] for i in sl] + [self.cs[i] for i in sl], [self.cl[i] for i in sl]):
+                for r, convs in enumerate(grp):
+                    self._lgroup[id(convs[0])] = (grp, r)
         # forward counters of the two ViT stages: a staged backward (_MCMEncFn / _MCMDecFn) refuses activations a later
         # forward of that stage -- or a whole forward -- replaced
         self.enc_gen = self.dec_gen = 0
@@ -655,10 +215,11 @@ class TrainExec(_VitTrainBase):
                           table=torch.empty((N, 59), dtype=torch.float32, device=self.device))
 
         # ---- h_s (MCM.py:747-748): mean straight into the first M columns of LMS = [latent_means | y_hat slots]
-        # h_s_scale into the first M columns of LS, rows 2M apart like LMS: the mean and scale stacks of a slice
-        # then read their inputs with one layout and run as one 2-problem launch per layer (_slices_fwd)
-        self.LMS = self._z(self.Mp, 2 * M, dtype=dt)
-        self.LS = self._e(self.Mp, 2 * M)
+        # h_s_scale into the first M columns of LS, rows 2M apart like LMS and one [Mp][2M] block after it: the mean
+        # and scale stacks of a slice then read their inputs with one layout, Mp * 2M elements apart, and run as one
+        # 2-problem launch per layer (_group_fwd).  Only LMS is zeroed (the y_hat slots not written yet)
+        self.LMS, self.LS = self._e(2, self.Mp, 2 * M).unbind(0)
+        self.LMS.zero_()
         self.hs_mean = self._h_s_fwd(m.h_s_mean, self.LMS, 2 * M)
         self.hs_scale = self._h_s_fwd(m.h_s_scale, self.LS, 2 * M)
 
@@ -756,16 +317,14 @@ class TrainExec(_VitTrainBase):
           * slices ms..S-1 batched: one launch for their 2 x nbs mean / scale stacks, the likelihoods, one for their
             lrp stacks.
         Weights are packed in fragment order by the per-step relayout (relayout mode 3).  Returns nothing; fills
-        self.sl with the records _slices_bwd reads (same shapes as _slices_fwd's)."""
+        self.sl with the records _slices_bwd reads (same shapes as _group_fwd's)."""
         m, dt, W, B, g = self.m, self.dtype, self.w, self.batch, self.g
         M, S, sw, ms, Mp, HW = m.latent_depth, m.num_slices, self.sw, self.ms, self.Mp, g * g
         mid = self.mid
         c0, nl = mid[0], len(mid)
         esz, e4 = self.LMS.element_size(), 4
         lms = self.LMS.data_ptr()
-        cm = [_convs(m.cc_transform_mean[i]) for i in range(S)]
-        cs = [_convs(m.cc_transform_scale[i]) for i in range(S)]
-        cl = [_convs(m.lrp_transform[i]) for i in range(S)]
+        cm, cs, cl = self.cm, self.cs, self.cl
         self.YPT = self._e(Mp, M)
         self.YPRE = torch.empty((Mp, M), dtype=torch.float32, device=self.device)
         self.YH = self._e(Mp, M)
@@ -865,79 +424,68 @@ class TrainExec(_VitTrainBase):
                           "scale": [(a[1, j], p_[1, j]) for a, p_ in sv_b] + [MSB[1, j]],
                           "lrp": [(a[j], p_[j]) for a, p_ in sv_lb] + [tb[j]]}
 
+    def _pack(self, stacks, l, kind, what="weight"):
+        """layer l's `kind` copies of the weights (or what="bias") of `stacks` (conv lists: consecutive stacks of one
+        launch group) as rows of the group's pack -> (the first stack's row, the element stride to the next one's)"""
+        grp, r = self._lgroup[id(stacks[0][0])]
+        if any(grp[r + j] is not c for j, c in enumerate(stacks)):
+            raise RuntimeError("slice stacks of one launch must be consecutive stacks of one launch group")
+        pack = self.w.packed([getattr(c[l], what) for c in grp], kind)
+        return pack[r], pack[0].numel()
+
     def _slices_fwd(self):
         # the fused stack backward reads what the fused forward saved (bf16 pre-activations, [problems][Mp][c])
         self._fused_bwd = self._fused_ok() and self.USE_LIC_STACK_BWD
         if self._fused_ok():
             return self._slices_fwd_fused()
-        m, dt, W, B, g = self.m, self.dtype, self.w, self.batch, self.g
-        M, S, sw, ms, Mp, HW = m.latent_depth, m.num_slices, self.sw, self.ms, self.Mp, self.g * self.g
-        esz = self.LMS.element_size()
-        lms = self.LMS.data_ptr()
+        m, g, Mp = self.m, self.g, self.Mp
+        M = m.latent_depth
         self.YPT = self._e(Mp, M)
         self.YPRE = torch.empty((Mp, M), dtype=torch.float32, device=self.device)
         self.YH = self._e(Mp, M)
-        self.YLIK = torch.empty((B, M, g, g), dtype=torch.float32, device=self.device)
+        self.YLIK = torch.empty((self.batch, M, g, g), dtype=torch.float32, device=self.device)
         self.sl = []
-        # slices 0..ms-1 in order (each conditions on the ones before); slices ms..S-1 all condition on y_hat
-        # slots 0..ms-1 only (max_support_slices, MCM.py:73, 756-758), so they run batched (_batched_fwd)
-        nser = ms if S - ms > 1 else S
-        for i in range(nser):
-            k = min(i, ms)
-            cin_m = M + sw * k
-            rec = {}
-            rec["mean"], rec["scale"] = self._ms_fwd(i, k)
-            mu, sig = rec["mean"][-1], rec["scale"][-1]
-            ops.gc_slices(self.Y32, M, i * sw, mu, sig, 0, sw, self.y_noise, self.YLIK, M, self.YPT, dt, M,
-                          self.YPRE, M, B, HW, 1, sw)
-            ypt = self.YPT.data_ptr() + i * sw * esz
-            rec["lrp"] = self._stack_fwd(_convs(m.lrp_transform[i]), (self.LMS, cin_m, 2 * M, ypt, sw, M), lrp=i)
-            self.sl.append(rec)
-        if nser < S:
-            self.sl += self._batched_fwd(nser, S - nser)
+        for i0, nbs in self.slice_groups:
+            self.sl += self._group_fwd(i0, nbs, min(i0, self.ms))
 
-    def _batched_fwd(self, i0, nbs):
-        """slices i0..i0+nbs-1 together: their mean / scale stacks as one 2 x nbs-problem launch per layer, the
-        Gaussian likelihoods of all nbs slices in one launch, their lrp stacks as one nbs-problem launch per layer
-        (weights / biases of each group packed so problem j sits at a constant stride).  Same arithmetic per
-        slice as the serial form; returns one saved-activation record per slice"""
-        m, dt, W, B, g, Mp = self.m, self.dtype, self.w, self.batch, self.g, self.Mp
+    def _group_fwd(self, i0, nbs, k):
+        """slices i0..i0+nbs-1 on the support slots 0..k-1 (MCM.py:761-787), one conv launch per layer: their mean and
+        scale stacks as 2 x nbs problems (problem (0, j) reads [latent_means | slots] from LMS, (1, j) [latent_scales |
+        the same slots] from LS), the Gaussian likelihoods of the nbs slices, their lrp stacks as nbs problems.  Every
+        per-problem stride is a shape product: weights and biases come from the launch group's packs, outputs are
+        [2][nbs][Mp][cout] / [nbs][Mp][cout].  Returns one saved-activation record per slice,
+        {"mean": [(act, pre) x 4, out], "scale": the same, "lrp": [(act, pre) x 4, t]}"""
+        m, dt, B, g, Mp = self.m, self.dtype, self.batch, self.g, self.Mp
         M, sw, HW = m.latent_depth, self.sw, g * g
-        k = self.ms  # support slots of every batched slice
         esz = self.LMS.element_size()
         sl = range(i0, i0 + nbs)
-        cm = [_convs(m.cc_transform_mean[i]) for i in sl]
-        cs = [_convs(m.cc_transform_scale[i]) for i in sl]
-        cl = [_convs(m.lrp_transform[i]) for i in sl]
+        cms = [self.cm[i] for i in sl] + [self.cs[i] for i in sl]
+        cl = [self.cl[i] for i in sl]
         recs = [{"mean": [], "scale": [], "lrp": []} for _ in sl]
-        x1, c1, ld1 = self.LMS, M, 2 * M
-        x1s = ((self.LS.data_ptr() - self.LMS.data_ptr()) // esz, 0)
-        x2, c2 = self.LMS.data_ptr() + M * esz, sw * k
-        nl = len(cm[0])
+        nl = len(cl[0])
+        x1, c1, ld1, x1s = self.LMS, M, 2 * M, (Mp * 2 * M, 0)
+        x2, c2 = (self.LMS.data_ptr() + M * esz if k else None), sw * k
         for l in range(nl):
-            cout = cm[0][l].out_channels
-            wm_, ws_ = W.packed([c[l].weight for c in cm], "conv"), W.packed([c[l].weight for c in cs], "conv")
-            bm_, bs_ = W.packed([c[l].bias for c in cm], "bias"), W.packed([c[l].bias for c in cs], "bias")
-            st = {"x1": x1s, "w": ((ws_.data_ptr() - wm_.data_ptr()) // wm_.element_size(), wm_[0].numel()),
-                  "b": ((bs_.data_ptr() - bm_.data_ptr()) // 4, cout), "y": (nbs * Mp * cout, Mp * cout)}
+            cout = cms[0][l].out_channels
+            (w, ws), (b, bs) = self._pack(cms, l, "conv"), self._pack(cms, l, "bias", "bias")
+            st = {"x1": x1s, "w": (nbs * ws, ws), "b": (nbs * bs, bs), "y": (nbs * Mp * cout, Mp * cout)}
             if l < nl - 1:
                 act, pre = self._e(2, nbs, Mp, cout), self._e(2, nbs, Mp, cout)
                 st["pre"] = st["y"]
-                ops.conv3x3(x1, c1, ld1, B, g, g, wm_, bm_, act, cout, cout, dt, act=ACT_GELU, x2=x2, c2=c2, ld2=2 * M,
+                ops.conv3x3(x1, c1, ld1, B, g, g, w, b, act, cout, cout, dt, act=ACT_GELU, x2=x2, c2=c2, ld2=2 * M,
                             pre=pre, ldp=cout, nb=(2, nbs), strides=st)
                 for j in range(nbs):
                     recs[j]["mean"].append((act[0, j], pre[0, j]))
                     recs[j]["scale"].append((act[1, j], pre[1, j]))
-                x1, c1, ld1, x1s, x2, c2 = act, cout, cout, (nbs * Mp * cout, Mp * cout), None, 0
+                x1, c1, ld1, x1s, x2, c2 = act, cout, cout, st["y"], None, 0
             else:
-                out = torch.empty((2, nbs, Mp, cout), dtype=torch.float32, device=self.device)
-                ops.conv3x3(x1, c1, ld1, B, g, g, wm_, bm_, out, cout, cout, dt, y_f32=True, x2=x2, c2=c2, ld2=2 * M,
+                mus = torch.empty((2, nbs, Mp, cout), dtype=torch.float32, device=self.device)
+                ops.conv3x3(x1, c1, ld1, B, g, g, w, b, mus, cout, cout, dt, y_f32=True, x2=x2, c2=c2, ld2=2 * M,
                             nb=(2, nbs), strides=st)
                 for j in range(nbs):
-                    recs[j]["mean"].append(out[0, j])
-                    recs[j]["scale"].append(out[1, j])
-                mus = out
-        # GaussianConditional + quantize_ste of all nbs slices (mu / sigma blocks Mp * sw apart)
+                    recs[j]["mean"].append(mus[0, j])
+                    recs[j]["scale"].append(mus[1, j])
+        # GaussianConditional + quantize_ste of the nbs slices (mu / sigma blocks Mp * sw apart)
         ops.gc_slices(self.Y32, M, i0 * sw, mus[0], mus[1], Mp * sw, sw, self.y_noise, self.YLIK, M, self.YPT, dt, M,
                       self.YPRE, M, B, HW, nbs, sw)
         # lrp stacks: input [latent_means | slots 0..k-1] (shared) + this slice's y_hat_pre (x2, sw apart)
@@ -945,96 +493,28 @@ class TrainExec(_VitTrainBase):
         x2, c2, ld2, x2s = self.YPT.data_ptr() + i0 * sw * esz, sw, M, (0, sw)
         for l in range(nl):
             cout = cl[0][l].out_channels
-            wl_, bl_ = W.packed([c[l].weight for c in cl], "conv"), W.packed([c[l].bias for c in cl], "bias")
-            st = {"x1": x1s, "x2": x2s, "w": (0, wl_[0].numel()), "b": (0, cout)}
+            (w, ws), (b, bs) = self._pack(cl, l, "conv"), self._pack(cl, l, "bias", "bias")
+            st = {"x1": x1s, "x2": x2s, "w": (0, ws), "b": (0, bs)}
             if l < nl - 1:
                 act, pre = self._e(nbs, Mp, cout), self._e(nbs, Mp, cout)
                 st["y"] = st["pre"] = (0, Mp * cout)
-                ops.conv3x3(x1, c1, ld1, B, g, g, wl_, bl_, act, cout, cout, dt, act=ACT_GELU, x2=x2, c2=c2, ld2=ld2,
+                ops.conv3x3(x1, c1, ld1, B, g, g, w, b, act, cout, cout, dt, act=ACT_GELU, x2=x2, c2=c2, ld2=ld2,
                             pre=pre, ldp=cout, nb=(1, nbs), strides=st)
                 for j in range(nbs):
                     recs[j]["lrp"].append((act[j], pre[j]))
-                x1, c1, ld1, x1s, x2, c2, ld2, x2s = act, cout, cout, (0, Mp * cout), None, 0, 0, (0, 0)
+                x1, c1, ld1, x1s, x2, c2, ld2, x2s = act, cout, cout, st["y"], None, 0, 0, (0, 0)
             else:
-                # y_hat = y_hat_pre + 0.5 tanh(t) into YH (slice j at channels (i0 + j) sw), t kept in f32
+                # y_hat = y_hat_pre + 0.5 tanh(t) into YH (slice j at channels (i0 + j) sw) and, for a slice below ms,
+                # into its support slot of LMS; t kept in f32
                 t = torch.empty((nbs, Mp, cout), dtype=torch.float32, device=self.device)
-                st.update({"y": (0, sw), "src": (0, sw), "pre": (0, Mp * cout)})
-                ops.conv3x3(x1, c1, ld1, B, g, g, wl_, bl_, self.YH.data_ptr() + i0 * sw * esz, M, cout, dt,
+                st.update({"y": (0, sw), "src": (0, sw), "y2": (0, sw), "pre": (0, Mp * cout)})
+                ops.conv3x3(x1, c1, ld1, B, g, g, w, b, self.YH.data_ptr() + i0 * sw * esz, M, cout, dt,
                             y_f32=(dt == torch.float32), lrp_src=self.YPRE.data_ptr() + i0 * sw * 4, ld_src=M,
+                            y2=(self.LMS.data_ptr() + (M + i0 * sw) * esz) if i0 < self.ms else None, ldy2=2 * M,
                             pre=t, ldp=cout, nb=(1, nbs), strides=st)
                 for j in range(nbs):
                     recs[j]["lrp"].append(t[j])
         return recs
-
-    def _ms_fwd(self, i, k):
-        """cc_transform_mean[i] and cc_transform_scale[i] (MCM.py:761-768) as one 2-problem conv launch per layer:
-        problem 0 reads [latent_means | y_hat slots 0..k-1] from LMS, problem 1 [latent_scales | the same slots]
-        (LS and LMS share the 2M row pitch; per-problem weight / bias / input offsets are pointer differences).
-        Returns the saved activations of each stack as _stack_fwd does."""
-        m, dt, W, B, g, Mp = self.m, self.dtype, self.w, self.batch, self.g, self.Mp
-        M, sw = m.latent_depth, self.sw
-        cm, cs = _convs(m.cc_transform_mean[i]), _convs(m.cc_transform_scale[i])
-        esz = self.LMS.element_size()
-
-        def diff(a, b, e):
-            d = b.data_ptr() - a.data_ptr()
-            assert d % e == 0
-            return d // e
-
-        sv_m, sv_s = [], []
-        x1, ld1, xs = self.LMS, 2 * M, diff(self.LMS, self.LS, esz)
-        c1, c2 = M, sw * k
-        x2 = self.LMS.data_ptr() + M * esz if k else None
-        for l, (a, b) in enumerate(zip(cm, cs)):
-            cout = a.out_channels
-            wa, wb = W.conv(a.weight), W.conv(b.weight)
-            st = {"x1": (xs, 0), "w": (diff(wa, wb, wa.element_size()), 0),
-                  "b": (diff(a.bias, b.bias, 4), 0), "y": (Mp * cout, 0)}
-            if l < 4:
-                act, pre = self._e(2, Mp, cout), self._e(2, Mp, cout)
-                st["pre"] = (Mp * cout, 0)
-                ops.conv3x3(x1, c1, ld1, B, g, g, wa, a.bias.detach(), act, cout, cout, dt, act=ACT_GELU, x2=x2, c2=c2,
-                            ld2=2 * M, pre=pre, ldp=cout, nb=(2, 1), strides=st)
-                sv_m.append((act[0], pre[0]))
-                sv_s.append((act[1], pre[1]))
-                x1, c1, ld1, xs, x2, c2 = act, cout, cout, Mp * cout, None, 0
-            else:
-                out = torch.empty((2, Mp, cout), dtype=torch.float32, device=self.device)
-                ops.conv3x3(x1, c1, ld1, B, g, g, wa, a.bias.detach(), out, cout, cout, dt, y_f32=True, x2=x2, c2=c2,
-                            ld2=2 * M, nb=(2, 1), strides=st)
-                sv_m.append(out[0])
-                sv_s.append(out[1])
-        return sv_m, sv_s
-
-    def _stack_fwd(self, convs, first, lrp=None):
-        """5-conv stack (cc_transform / lrp_transform): returns [(act_l, pre_l) for l < 4] + [out]"""
-        dt, W, B, g, Mp = self.dtype, self.w, self.batch, self.g, self.Mp
-        m = self.m
-        M, sw = m.latent_depth, self.sw
-        x1, c1, ld1, x2, c2, ld2 = first
-        saved = []
-        for l, c in enumerate(convs):
-            cout = c.out_channels
-            if l < 4:
-                act, pre = self._e(Mp, cout), self._e(Mp, cout)
-                ops.conv3x3(x1, c1, ld1, B, g, g, W.conv(c.weight), c.bias.detach(), act, cout, cout, dt, act=ACT_GELU,
-                            x2=x2, c2=c2, ld2=ld2, pre=pre, ldp=cout)
-                saved.append((act, pre))
-                x1, c1, ld1, x2, c2, ld2 = act, cout, cout, None, 0, 0
-            elif lrp is None:
-                out = torch.empty((Mp, cout), dtype=torch.float32, device=self.device)
-                ops.conv3x3(x1, c1, ld1, B, g, g, W.conv(c.weight), c.bias.detach(), out, cout, cout, dt, y_f32=True)
-                saved.append(out)
-            else:
-                i = lrp
-                esz = self.YH.element_size()
-                t = torch.empty((Mp, cout), dtype=torch.float32, device=self.device)
-                ops.conv3x3(x1, c1, ld1, B, g, g, W.conv(c.weight), c.bias.detach(), self.YH.data_ptr() + i * sw * esz,
-                            M, cout, dt, y_f32=(dt == torch.float32), lrp_src=self.YPRE.data_ptr() + i * sw * 4,
-                            ld_src=M, y2=(self.LMS.data_ptr() + (M + i * sw) * esz) if i < self.ms else None,
-                            ldy2=2 * M, pre=t, ldp=cout)
-                saved.append(t)
-        return saved
 
     # ------------------------------------------------------------------ backward
     def backward(self, dxhat, dylik, dzlik, gflat, sync=None):
@@ -1223,39 +703,36 @@ class TrainExec(_VitTrainBase):
                 d = dx
 
     def _slices_bwd(self, dYH, dylik):
-        m, dt, W, G, B, g = self.m, self.dtype, self.w, self.grad, self.batch, self.g
+        m, dt, B, g = self.m, self.dtype, self.batch, self.g
         M, S, sw, ms, Mp, HW = m.latent_depth, m.num_slices, self.sw, self.ms, self.Mp, g * g
         esz = self.LMS.element_size()
         lms = self.LMS.data_ptr()
         DY = self._z(Mp, M)
-        dLM = self._z(Mp, M)
-        dLS = self._z(Mp, M)
-        dSUP = self._z(Mp, M)
+        dLM, dLS = self._z(2, Mp, M).unbind(0)
         # The scale stack of a slice depends on nothing the mean stack writes: eager on a GPU it runs on its own
         # stream beside the mean stack, its support-channel gradients in their own buffer (dSUP2, added where slice
         # j's lrp backward reads column block j), so the two data-gradient chains never touch the same accumulator.
         # Not under graph capture: HIP's graph executor ran that topology 3.4 ms slower per step (31.4 -> 34.8 ms;
         # eager 31.9 -> 31.4), and 6.5 ms slower with joins only where slices <= 5 read dSUP2 (31.9 -> 38.4), so a
         # captured step keeps both stacks on the compute stream, their layers 4..1 as 2-problem data-gradient
-        # launches (_stack_bwd_pair; same sums either way).
+        # launches (same sums either way).  dSUP2 also without the stream: the same sums in the same order.
+        dSUP, dSUP2 = self._z(2, Mp, M).unbind(0)
         conc = self._side is not None and not torch.cuda.is_current_stream_capturing()
         if conc and "_scale_stream" not in self.__dict__:
             self._scale_stream = torch.cuda.Stream(device=self.device)
-        dSUP2 = self._z(Mp, M)  # also without the stream: the same sums in the same order either way
         main = torch.cuda.current_stream(self.device) if conc else None
         joined = None
         deferred = []  # eager only: (slice, mean stack's, scale stack's layer 4..1 weight gradients)
         GS = torch.empty((Mp, M), dtype=torch.float32, device=self.device)
-        # slices ms..S-1 were run batched in the forward (they condition on the fixed support slots 0..ms-1): their
+        # slices nser..S-1 ran as one group in the forward (they condition on the fixed support slots 0..ms-1): their
         # backward is batched too, every data gradient of layers 4..1 one launch for all of them
-        nser = ms if S - ms > 1 else S
-        if nser < S:
-            self._batched_bwd(nser, S - nser, dYH, dylik, DY, dLM, dLS, dSUP, dSUP2, GS)
-        for i in reversed(range(nser)):
+        if self.nser < S:
+            self._batched_bwd(self.nser, S - self.nser, dYH, dylik, DY, dLM, dLS, dSUP, dSUP2, GS)
+        for i in reversed(range(self.nser)):
             # fresh per slice: the side stream's weight gradients of slice i + 1 may still read the last ones
             dT = self._e(Mp, sw)
-            dMU, dSG = self._e(Mp, sw), self._e(Mp, sw)
-            k = min(i, ms)
+            dMU, dSG = self._e(2, Mp, sw).unbind(0)
+            k = i  # support slots of a serial slice
             cin_m = M + sw * k
             rec = self.sl[i]
             gs_i = GS.data_ptr() + i * sw * 4
@@ -1266,34 +743,36 @@ class TrainExec(_VitTrainBase):
             T.lrp_bwd(rec["lrp"][-1], sw, dT, sw, Mp, sw, dt, g32=(dSUP.data_ptr() + i * sw * 4) if i < ms else None,
                       ld32=M, g16=dYH.data_ptr() + i * sw * esz, ld16=M, gsum=gs_i, ldgs=M,
                       g32b=(dSUP2.data_ptr() + i * sw * 4) if i < ms else None, ld32b=M)
-            self._stack_bwd(_convs(m.lrp_transform[i]), rec["lrp"], dT,
-                            (self.LMS, cin_m, 2 * M, self.YPT.data_ptr() + i * sw * esz, sw, M),
-                            [(dLM, M, M), (dSUP, M, sw * k), (gs_i, M, sw)])
+            self._stack_bwd([(self.cl[i], rec["lrp"], dT,
+                              (self.LMS, cin_m, 2 * M, self.YPT.data_ptr() + i * sw * esz, sw, M),
+                              [(dLM, M, M), (dSUP, M, sw * k), (gs_i, M, sw)])])
             # GaussianConditional + quantize_ste (MCM.py:771-776)
             T.gc_bwd(self.Y32, M, i * sw, rec["mean"][-1], rec["scale"][-1], sw, self.y_noise, M, dylik, GS, M, DY, M,
                      dMU, dSG, sw, B, HW, sw, dt)
-            scale_args = (_convs(m.cc_transform_scale[i]), rec["scale"], dSG,
-                          (self.LS, M, 2 * M, lms + M * esz if k else None, sw * k, 2 * M),
-                          [(dLS, M, M), (dSUP2, M, sw * k)])
-            mean_args = (_convs(m.cc_transform_mean[i]), rec["mean"], dMU, (self.LMS, cin_m, 2 * M, None, 0, 0),
-                         [(dLM, M, M), (dSUP, M, sw * k)])
+            scale = (self.cs[i], rec["scale"], dSG, (self.LS, M, 2 * M, lms + M * esz if k else None, sw * k, 2 * M),
+                     [(dLS, M, M), (dSUP2, M, sw * k)])
+            mean = (self.cm[i], rec["mean"], dMU, (self.LMS, cin_m, 2 * M, None, 0, 0),
+                    [(dLM, M, M), (dSUP, M, sw * k)])
             if not conc:
                 # one stream: layers 4..1 of both stacks as 2-problem data-gradient launches
-                self._stack_bwd_pair(mean_args, scale_args)
-                self._ready(_convs(m.cc_transform_scale[i])[0].bias)
+                self._stack_bwd([mean, scale])
+                self._ready(self.cs[i][0].bias)
                 continue
-            # eager: the scale stack on its own stream, the mean stack first on the compute stream.  Their layers
-            # 4..1 weight gradients wait for the final join and then run as the same 2-problem launches a captured
-            # step issues (_stack_bwd_pair), so eager and graphed steps sum them with one split plan; the DP
-            # hand-offs of these slices follow them.
+            # eager: the scale stack on its own stream, the mean stack first on the compute stream (one-problem
+            # launches on rows 0 and 1 of the pair's weight packs).  Their layers 4..1 weight gradients wait for the
+            # final join and then run as the same 2-problem launches a captured step issues, so eager and graphed
+            # steps sum them with one split plan; the DP hand-offs of these slices follow them.
             fork = torch.cuda.Event()
             fork.record(main)
             im, is_ = [], []
-            self._stack_bwd(*mean_args, defer=im)
+            built = self.w.builds
+            self._stack_bwd([mean], defer=im)
             ss = self._scale_stream
             ss.wait_event(fork)
+            if self.w.builds != built:  # (first step) the pair's packs were just built on this stream, row 1 too
+                ss.wait_stream(main)
             with torch.cuda.stream(ss):
-                self._stack_bwd(*scale_args, defer=is_)
+                self._stack_bwd([scale], defer=is_)
             joined = torch.cuda.Event()
             joined.record(ss)
             self._keep.append(dSG)  # read on the scale stream; freed after the backward's join
@@ -1302,73 +781,31 @@ class TrainExec(_VitTrainBase):
             main.wait_event(joined)
         for i, im, is_ in deferred:
             for (ia, shp), (ib, _) in zip(im, is_):
-                self._wg_many([ia, ib], *shp, layout="conv")
+                self._wg_many(ia + ib, *shp, layout="conv")
             self._wg_flush()
-            self._ready(_convs(m.cc_transform_scale[i])[0].bias)
+            self._ready(self.cs[i][0].bias)
         return DY, dLM, dLS
 
     def _batched_bwd(self, i0, nbs, dYH, dylik, DY, dLM, dLS, dSUP, dSUP2, GS):
-        """backward of the batched slices i0..i0+nbs-1 (_batched_fwd): per slice the lrp backward, then the lrp stacks'
-        layers 4..1 as ONE nbs-problem data-gradient launch each, their first layers one by one (routes into the
-        shared latent / support gradients, slices in descending order), the Gaussian backward per slice, then the
-        mean and scale stacks' layers 4..1 as ONE 2 nbs-problem launch each and their first layers one by one (mean
-        before scale per slice).  Weight gradients per problem on the side stream, as for the serial slices."""
+        """backward of the slice group i0..i0+nbs-1 (_group_fwd, nbs > 1): per slice the lrp backward, then the lrp
+        stacks' layers 4..1 (_stacks_bwd), their first layers one by one (routes into the shared latent / support
+        gradients, slices in descending order), the Gaussian backward per slice, then the mean and scale stacks' layers
+        4..1 as 2 nbs problems and their first layers one by one (mean before scale per slice).  Weight gradients per
+        problem group on the side stream, as for the serial slices."""
         m, dt, W, G, B, g = self.m, self.dtype, self.w, self.grad, self.batch, self.g
-        M, sw, ms, Mp, HW = m.latent_depth, self.sw, self.ms, self.Mp, g * g
+        M, sw, Mp, HW = m.latent_depth, self.sw, self.Mp, g * g
         esz = self.LMS.element_size()
         lms = self.LMS.data_ptr()
-        k = ms
+        k = self.ms
         sl = list(range(i0, i0 + nbs))
         recs = [self.sl[i] for i in sl]
-        cl = [_convs(m.lrp_transform[i]) for i in sl]
-        cm = [_convs(m.cc_transform_mean[i]) for i in sl]
-        cs = [_convs(m.cc_transform_scale[i]) for i in sl]
-
-        def stride(views, what):
-            """constant element stride between consecutive problems' views (the batched forward's buffers)"""
-            d = {(b.data_ptr() - a.data_ptr()) for a, b in zip(views, views[1:])}
-            e = views[0].element_size()
-            if len(d) > 1 or (d and next(iter(d)) % e):
-                raise RuntimeError(f"batched slice backward: {what} not at a constant stride")
-            return (next(iter(d)) // e) if d else 0
-
-        def stacks(convs, saved, dtop, what, groups=1):
-            """layers 4..1 of len(convs) same-shape stacks, problem p's saved activations saved[p]; dtop [P][Mp][cout];
-            the weight gradients of each of `groups` consecutive problem groups (lrp / mean / scale) as one batched
-            launch per layer"""
-            P = len(convs)
-            fd = self._fused_dgrads([(convs[p_], saved[p_], dtop[p_]) for p_ in range(P)])
-            if fd is not None:  # the data gradients in one launch, then the weight gradients per layer
-                for l in range(4, 0, -1):
-                    cin, cout = convs[0][l].in_channels, convs[0][l].out_channels
-                    q = P // groups
-                    for g0 in range(0, P, q):
-                        self._wg_many([{"a": fd[l][p_], "b": saved[p_][l - 1][0], "out": G(convs[p_][l].weight),
-                                        "bias": G(convs[p_][l].bias)} for p_ in range(g0, g0 + q)],
-                                      cout, 9 * cin, Mp, dt, conv=dict(c1=cin, H=g, W=g, cin=cin), layout="conv")
-                return fd[0]
-            d = dtop
-            for l in range(4, 0, -1):
-                cin, cout = convs[0][l].in_channels, convs[0][l].out_channels
-                q = P // groups
-                for g0 in range(0, P, q):
-                    self._wg_many([{"a": d[p_], "b": saved[p_][l - 1][0], "out": G(convs[p_][l].weight),
-                                    "bias": G(convs[p_][l].bias)} for p_ in range(g0, g0 + q)],
-                                  cout, 9 * cin, Mp, dt, conv=dict(c1=cin, H=g, W=g, cin=cin), layout="conv")
-                wd = W.packed([c[l].weight for c in convs], "conv_dg")
-                pres = [saved[p_][l - 1][1] for p_ in range(P)]
-                dx = self._e(P, Mp, cin)
-                T.conv_dgrad(d[0], wd[0], B, g, g, 1, cout, cin, dt, out=dx[0], pre=pres[0],
-                             batch=(P, Mp * cout, wd[0].numel(), Mp * cin, stride(pres, what + " pre")))
-                d = dx
-            return d
-
+        cl, cm, cs = ([c[i] for i in sl] for c in (self.cl, self.cm, self.cs))
         # ---- lrp: y_hat = y_hat_pre + 0.5 tanh(t) backward, per slice (no support gradients beyond slot ms - 1)
         dT = self._e(nbs, Mp, sw)
         for j, i in enumerate(sl):
             T.lrp_bwd(recs[j]["lrp"][-1], sw, dT[j], sw, Mp, sw, dt, g16=dYH.data_ptr() + i * sw * esz, ld16=M,
                       gsum=GS.data_ptr() + i * sw * 4, ldgs=M)
-        dl = stacks(cl, [r["lrp"] for r in recs], dT, "lrp")
+        dl, _ = self._stacks_bwd([(cl[j], recs[j]["lrp"], dT[j]) for j in range(nbs)])
         cin, cout = M + sw * k + sw, cl[0][0].out_channels
         self._wg_many([{"a": dl[j], "b": self.LMS, "x2": self.YPT.data_ptr() + i * sw * esz, "out": G(cl[j][0].weight),
                         "bias": G(cl[j][0].bias)} for j, i in enumerate(sl)],
@@ -1384,10 +821,11 @@ class TrainExec(_VitTrainBase):
         for j, i in enumerate(sl):
             T.gc_bwd(self.Y32, M, i * sw, recs[j]["mean"][-1], recs[j]["scale"][-1], sw, self.y_noise, M, dylik, GS, M,
                      DY, M, dMS[0, j], dMS[1, j], sw, B, HW, sw, dt)
-        dms = stacks(cm + cs, [r["mean"] for r in recs] + [r["scale"] for r in recs], dMS.view(2 * nbs, Mp, sw),
-                     "mean/scale", groups=2)
-        firsts = ((cm, (self.LMS, M + sw * k, 2 * M, None, 0, 0), lambda j: [(dLM, M, M), (dSUP, M, sw * k)]),
-                  (cs, (self.LS, M, 2 * M, lms + M * esz, sw * k, 2 * M), lambda j: [(dLS, M, M), (dSUP2, M, sw * k)]))
+        dms, _ = self._stacks_bwd([(c[j], recs[j][key], dMS[t, j]) for t, (c, key) in enumerate(((cm, "mean"),
+                                                                                                (cs, "scale")))
+                                   for j in range(nbs)], groups=2)
+        firsts = ((cm, (self.LMS, M + sw * k, 2 * M, None, 0, 0), [(dLM, M, M), (dSUP, M, sw * k)]),
+                  (cs, (self.LS, M, 2 * M, lms + M * esz, sw * k, 2 * M), [(dLS, M, M), (dSUP2, M, sw * k)]))
         for t, (convs, first, _) in enumerate(firsts):
             x1, c1, ld1, x2, c2, ld2 = first
             cin, cout = c1 + c2, convs[0][0].out_channels
@@ -1398,9 +836,71 @@ class TrainExec(_VitTrainBase):
             for t, (convs, first, routes) in enumerate(firsts):
                 c, d = convs[j][0], dms[t * nbs + j]
                 cin, cout = first[1] + first[4], c.out_channels
-                T.conv_dgrad(d, W.conv_dg(c.weight), B, g, g, 1, cout, cin, dt, routes=routes(j))
+                T.conv_dgrad(d, W.conv_dg(c.weight), B, g, g, 1, cout, cin, dt, routes=routes)
             self._wg_flush()
             self._ready(cs[j][0].bias)  # every gradient of slices >= i0 + j is final (DP hand-off per slice)
+
+    def _stack_bwd(self, stacks, defer=None):
+        """backward of a serial slice's stacks run together, stacks = [(convs, saved, dtop, first, routes)]: one (its
+        lrp stack; its mean or scale stack on a stream of its own) or two (mean, scale).  Layers 4..1 by _stacks_bwd;
+        then the first layers with their own input splits `first` = (x1, c1, ld1, x2, c2, ld2) and routes, one by one
+        in order.  Zero-width routes (no support slices yet) stay in place: their limits still partition the channels"""
+        dt, G, B, g, Mp = self.dtype, self.grad, self.batch, self.g, self.Mp
+        d0, routed = self._stacks_bwd([s[:3] for s in stacks], routes=[s[4] for s in stacks], defer=defer)
+        for (convs, _, _, (x1, c1, ld1, x2, c2, ld2), routes), d in zip(stacks, d0):
+            c = convs[0]
+            cin, cout = c1 + c2, c.out_channels
+            self._wg(d, x1, cout, 9 * cin, Mp, G(c.weight), dt, ldb=ld1,
+                     conv=dict(x2=x2, c1=c1, ld2=ld2, H=g, W=g, cin=cin), layout="conv", bias=G(c.bias))
+            if not routed:
+                T.conv_dgrad(d, self.w.conv_dg(c.weight), B, g, g, 1, cout, cin, dt, routes=routes)
+        self._wg_flush()
+
+    def _stacks_bwd(self, stacks, groups=1, routes=None, defer=None):
+        """layers 4..1 of P same-shape stacks, stacks = [(convs, saved, dtop)], consecutive stacks of one launch group
+        with their dtops and saved activations evenly spaced.  Data gradients: the fused chain (_fused_dgrads) when it
+        applies -- with `routes` (one list per problem) and FUSE_FIRST_DGRAD it adds the first layers' input gradients
+        too --, else one T.conv_dgrad per layer for the P problems on the group's packed "conv_dg" weights, outputs
+        [P][Mp][cin].  Weight gradients per layer through _wg_many, one call for each of `groups` runs of P / groups
+        problems, or appended to `defer` (a list) as (items, shape arguments) for the caller to issue.
+        -> (the gradients w.r.t. the first layers' pre-activations, one per problem; whether the chain has added the
+        first layers' input gradients)"""
+        dt, G, B, g, Mp = self.dtype, self.grad, self.batch, self.g, self.Mp
+        P, convs = len(stacks), [s[0] for s in stacks]
+        routes = routes if self.FUSE_FIRST_DGRAD else None
+        fd = self._fused_dgrads(stacks, routes)
+        d = [s[2] for s in stacks]
+
+        def even(views, what):
+            s = self._stride(views)
+            if s is None:
+                raise RuntimeError(f"slice stack backward: the problems' {what} are not at a constant stride")
+            return s
+
+        for l in range(4, 0, -1):
+            cin, cout = convs[0][l].in_channels, convs[0][l].out_channels
+            if fd is not None:
+                d = fd[l]
+            for g0 in range(0, P, P // groups):
+                items = [{"a": d[p], "b": stacks[p][1][l - 1][0], "out": G(convs[p][l].weight),
+                          "bias": G(convs[p][l].bias)} for p in range(g0, g0 + P // groups)]
+                shape = (cout, 9 * cin, Mp, dt, dict(c1=cin, H=g, W=g, cin=cin))
+                if defer is not None:
+                    defer.append((items, shape))
+                else:
+                    self._wg_many(items, *shape, layout="conv")
+            if fd is not None:
+                continue
+            wd, sw_ = self._pack(convs, l, "conv_dg")
+            pres = [s[1][l - 1][1] for s in stacks]
+            dx = self._e(P, Mp, cin)
+            T.conv_dgrad(d[0], wd, B, g, g, 1, cout, cin, dt, out=dx[0], pre=pres[0],
+                         batch=(P, even(d, "output gradients"), sw_, Mp * cin, even(pres, "pre-activations"))
+                         if P > 1 else None)
+            d = list(dx.unbind(0))
+        if fd is not None:
+            return fd[0], routes is not None
+        return d, False
 
     def _fused_dgrads(self, stacks, routes=None):
         """layers 4..1 data gradients of P same-shape stacks (convs, saved, dtop) in ONE tmae_lic_stack backward
@@ -1412,32 +912,30 @@ class TrainExec(_VitTrainBase):
         if not self._fused_bwd:
             return None
         P, Mp = len(stacks), self.Mp
-        convs0 = stacks[0][0]
-        couts = [c.out_channels for c in convs0]
-        if len(convs0) != 5 or any(c > ops.LSTK_MAXC for c in couts[:4]):
+        convs = [s[0] for s in stacks]
+        couts = [c.out_channels for c in convs[0]]
+        # P > 2: the chain has never run for more than two problems here (the stride check this one replaces compared
+        # every problem with the first and refused them); kept, because the chain and the per-layer launches round
+        # differently and the kernel is unmeasured there
+        if P > 2 or len(convs[0]) != 5 or any(c > ops.LSTK_MAXC for c in couts[:4]):
             return None
-
-        def delta(ts):
-            d = {t.data_ptr() - ts[0].data_ptr() for t in ts[1:]}
-            return 0 if not d else (next(iter(d)) // ts[0].element_size() if len(d) == 1 else None)
-
         dts = [s[2] for s in stacks]
         pres = [[s[1][l][1] for s in stacks] for l in (3, 2, 1, 0)]
-        sx = delta(dts)
-        if sx is None or any(p_[0].dtype != torch.bfloat16 or (P > 1 and delta(p_) != Mp * couts[l])
+        sx = self._stride(dts)
+        if sx is None or any(p_[0].dtype != torch.bfloat16 or (P > 1 and self._stride(p_) != Mp * couts[l])
                              for p_, l in zip(pres, (3, 2, 1, 0))):
             return None
-        ws = [self.w.packed([s[0][l].weight for s in stacks], "licT") for l in (4, 3, 2, 1)]
         outs = [self._e(P, Mp, couts[l]) for l in (3, 2, 1, 0)]
-        st = {"x1": (sx, 0)}
-        for k, l in enumerate((3, 2, 1, 0)):
-            st[f"w{k}"] = (ws[k][0].numel() if P > 1 else 0, 0)
-            st[f"s{k}"] = (Mp * couts[l], 0)
         lcouts = [couts[l] for l in (3, 2, 1, 0)]
-        if routes is not None:  # + the first layers' input gradients, routed
-            ws.append(self.w.packed([s[0][0].weight for s in stacks], "licT"))
-            st["w4"] = (ws[4][0].numel() if P > 1 else 0, 0)
-            lcouts.append(convs0[0].in_channels)
+        ws, st = [], {"x1": (sx, 0)}
+        for k, l in enumerate((4, 3, 2, 1, 0) if routes is not None else (4, 3, 2, 1)):
+            w, s = self._pack(convs, l, "licT")  # (layer 0: + the first layers' input gradients, routed)
+            ws.append(w)
+            st[f"w{k}"] = (s if P > 1 else 0, 0)
+        for k, c in enumerate(lcouts):
+            st[f"s{k}"] = (Mp * c, 0)
+        if routes is not None:
+            lcouts.append(convs[0][0].in_channels)
         ops.lic_stack_bwd(self.batch, self.g, dts[0], couts[4], couts[4], ws, lcouts, [p_[0] for p_ in pres], outs,
                           nb=(P, 1), strides=st, routes=routes)
         d = [None] * 5
@@ -1445,86 +943,6 @@ class TrainExec(_VitTrainBase):
             d[l] = [outs[k][p_] for p_ in range(P)]
         d[4] = dts
         return d
-
-    def _stack_bwd_pair(self, a, b):
-        """_stack_bwd of two stacks with the same layer shapes (a slice's mean and scale stacks): the data gradients
-        of layers 4..1 as one 2-problem launch (the fused chain, or one 2-problem conv launch per layer); the weight
-        gradients of layers 4..1 as 2-problem launches; the first layers (their own input splits / routes) one by one,
-        a's before b's"""
-        dt, W, G, B, g, Mp = self.dtype, self.w, self.grad, self.batch, self.g, self.Mp
-        (ca, sa, da, fa, ra), (cb, sb, db, fb, rb) = a, b
-        fd = self._fused_dgrads([(ca, sa, da), (cb, sb, db)], routes=[ra, rb] if self.FUSE_FIRST_DGRAD else None)
-        for l in range(4, 0, -1):
-            cin = ca[l].in_channels
-            dl = (fd[l][0], fd[l][1]) if fd is not None else (da, db)
-            self._wg_many([{"a": d, "b": saved[l - 1][0], "out": G(c.weight), "bias": G(c.bias)}
-                           for c, saved, d in ((ca[l], sa, dl[0]), (cb[l], sb, dl[1]))],
-                          ca[l].out_channels, 9 * cin, Mp, dt, conv=dict(c1=cin, H=g, W=g, cin=cin), layout="conv")
-            if fd is not None:
-                continue
-            cin, cout = ca[l].in_channels, ca[l].out_channels
-            assert (cb[l].in_channels, cb[l].out_channels) == (cin, cout)
-            dxa, dxb = self._e(Mp, cin), self._e(Mp, cin)
-            T.conv_dgrad(da, W.conv_dg(ca[l].weight), B, g, g, 1, cout, cin, dt, out=dxa, pre=sa[l - 1][1],
-                         second=(db, W.conv_dg(cb[l].weight), dxb, sb[l - 1][1]))
-            da, db = dxa, dxb
-        if fd is not None:
-            da, db = fd[0]
-        for c, d, first, routes in ((ca[0], da, fa, ra), (cb[0], db, fb, rb)):
-            x1, c1, ld1, x2, c2, ld2 = first
-            cin, cout = c1 + c2, c.out_channels
-            self._wg(d, x1, cout, 9 * cin, Mp, G(c.weight), dt, ldb=ld1,
-                     conv=dict(x2=x2, c1=c1, ld2=ld2, H=g, W=g, cin=cin), layout="conv", bias=G(c.bias))
-            if fd is None or not self.FUSE_FIRST_DGRAD:
-                T.conv_dgrad(d, W.conv_dg(c.weight), B, g, g, 1, cout, cin, dt, routes=routes)
-        self._wg_flush()
-
-    def _stack_bwd(self, convs, saved, dtop, first, routes, defer=None):
-        """backward of one 5-layer slice stack; with `defer` (a list) the weight gradients of layers 4..1 are
-        appended to it as (_wg_many item, shape args) instead of being queued"""
-        dt, W, G, B, g, Mp = self.dtype, self.w, self.grad, self.batch, self.g, self.Mp
-        fd = self._fused_dgrads([(convs, saved, dtop)], routes=[routes] if self.FUSE_FIRST_DGRAD else None)
-        d = dtop
-        for l in range(4, 0, -1):
-            c = convs[l]
-            cin, cout = c.in_channels, c.out_channels
-            act_prev, pre_prev = saved[l - 1]
-            if fd is not None:
-                d = fd[l][0]
-            if defer is not None:
-                defer.append(({"a": d, "b": act_prev, "out": G(c.weight), "bias": G(c.bias)},
-                              (cout, 9 * cin, Mp, dt, dict(c1=cin, H=g, W=g, cin=cin))))
-            else:
-                self._wg(d, act_prev, cout, 9 * cin, Mp, G(c.weight), dt, conv=dict(c1=cin, H=g, W=g, cin=cin),
-                         layout="conv", bias=G(c.bias))
-            if fd is not None:
-                continue
-            dx = self._e(Mp, cin)
-            T.conv_dgrad(d, W.conv_dg(c.weight), B, g, g, 1, cout, cin, dt, out=dx, pre=pre_prev)
-            d = dx
-        if fd is not None:
-            d = fd[0][0]
-        c = convs[0]
-        x1, c1, ld1, x2, c2, ld2 = first
-        cin, cout = c1 + c2, c.out_channels
-        self._wg(d, x1, cout, 9 * cin, Mp, G(c.weight), dt, ldb=ld1,
-                 conv=dict(x2=x2, c1=c1, ld2=ld2, H=g, W=g, cin=cin), layout="conv", bias=G(c.bias))
-        # zero-width routes (no support slices yet) stay in place: their limits still partition the channels
-        if fd is None or not self.FUSE_FIRST_DGRAD:
-            T.conv_dgrad(d, W.conv_dg(c.weight), B, g, g, 1, cout, cin, dt, routes=routes)
-        self._wg_flush()
-
-def _bias(b):
-    return None if b is None else b.detach()
-
-
-def _block_params(blk):
-    ps = [blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.norm2.weight, blk.norm2.bias,
-          blk.attn.proj.weight, blk.attn.proj.bias, blk.attn.qkv.weight]
-    if blk.attn.qkv.bias is not None:
-        ps.append(blk.attn.qkv.bias)
-    ps += [blk.norm1.weight, blk.norm1.bias]
-    return ps
 
 
 def _hs_layers(seq):

@@ -86,7 +86,7 @@ def wgrad(a, b, M, N, K, out, dtype, lda=None, ldb=None, a_remap=(None, 0, 0), b
     code = dtype_code(dtype)
     nb = batch[0] if batch is not None else 1
     need = _lib.value("tmae_wgrad_workspace_nb", M, N, K, code, int(slot_div), nb)
-    ws = scratch(dev, need, slot=ws_slot)  # slot 4: the side stream's weight gradients (mcm_train._wg)
+    ws = scratch(dev, need, slot=ws_slot)  # slot 4: the side stream's weight gradients (vit_train._VitTrainBase._wg)
     args = WgradArgs()
     args.a, args.lda = _p(a), (lda if lda is not None else M)
     G, Gs, off = a_remap
@@ -136,29 +136,14 @@ def dgrad_linear(dy, wt, M, N, K, dtype, out=None, pre=None, acc32=None, ldy=Non
 
 
 def conv_dgrad(dy, wd, n, H, W, stride, cout, cin, dtype, out=None, pre=None, ldy=None, ldo=None, ldp=None,
-               routes=None, out_f32=None, second=None, batch=None):
+               routes=None, out_f32=None, batch=None):
     """dx [n*H*W][cin] of a 3x3 conv from dy [n*Ho*Wo][cout]; wd = weight as [cin][3][3][cout] (dtype).
     routes: [(acc_f32, ld, ncols), ...] (<= 3, f32 +=, consecutive input-channel ranges).
-    second = (dy2, wd2, out2, pre2): a second problem of the same shape and layout in the same launch (no routes).
     batch = (nb, s_dy, s_wd, s_out, s_pre): nb problems, problem j's dy / wd / out / pre j * s elements past the
     first's (no routes)"""
     a = ConvDgradArgs()
     if batch is not None:
         a.nb, a.s_dy, a.s_wd, a.s_out, a.s_pre = batch
-    if second is not None:
-        def off(t2, t1, what):
-            if t2.dtype != t1.dtype:
-                raise ValueError(f"conv_dgrad second problem: {what} dtype {t2.dtype} != {t1.dtype}")
-            d = t2.data_ptr() - t1.data_ptr()
-            if d % t1.element_size():
-                raise ValueError(f"conv_dgrad second problem: {what} offset {d} B is not whole elements")
-            return d // t1.element_size()
-        dy2, wd2, out2, pre2 = second
-        a.nb = 2
-        a.s_dy, a.s_wd, a.s_out = off(dy2, dy, "dy"), off(wd2, wd, "wd"), off(out2, out, "out")
-        if (pre is None) != (pre2 is None):
-            raise ValueError("conv_dgrad second problem: pre given for one problem only")
-        a.s_pre = off(pre2, pre, "pre") if pre is not None else 0
     a.dy, a.ldy = _p(dy), ldy if ldy is not None else cout
     a.n, a.H, a.W, a.stride, a.cout, a.cin = n, H, W, stride, cout, cin
     a.wd = _p(wd)

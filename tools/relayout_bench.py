@@ -1,4 +1,4 @@
-"""Per-mode timing of the training step's weight re-layout (mcm_train._Weights.refresh -> tmae_relayout_multi) at
+"""Per-mode timing of the training step's weight re-layout (train_weights._Weights.refresh -> tmae_relayout_multi) at
 the bench config (ViT-B MCM, batch 64, bf16): one eager step fills the cache, then each group of entries (all, and
 each relayout mode alone) is marked stale and re-laid out; GPU time from events around the launch (a sleep kernel
 ahead of it hides the host's table work), bytes = f32 source read + destination written.

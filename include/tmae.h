@@ -443,6 +443,26 @@ long long tmae_image_scores_workspace(int n, int H, int W, int size); /* bytes *
 int tmae_image_scores(const unsigned char* gray, int n, int H, int W, int size, int patch, unsigned char* work,
                       long long work_bytes, float* scores, void* stream);
 
+/* ---------------------------------------------------------------- model inputs (utils/dataloader.py:57-73)
+ * The loader's transform after the decode: transforms.Resize((S, S), BICUBIC) on the PIL image, ToTensor and
+ * Normalize.  Pillow's 8-bit resample restated (csrc/resize.hip): src uint8 HWC [n][H][W][3] is resampled
+ * horizontally, then vertically, through a uint8 intermediate [n][H][Wo][3] in `work`; a pass whose input and
+ * output sizes are equal is skipped.  Per output value: clip8((2^21 + sum_t px[xmin + t] * kk[o][t]) >> 22).
+ * kk_h [Wo][ksize_h] / bounds_h [Wo][2] = (xmin, n) and kk_v [Ho][ksize_v] / bounds_v [Ho][2] are device int32
+ * tables built and validated on the host (ops.resize_tables; 0 <= xmin, n >= 1, xmin + n <= input size); the
+ * kernels clamp the tap ranges to the image all the same.  Equal to PIL.Image.resize bit for bit.
+ * out: TMAE_RESIZE_U8_HWC uint8 [n][Ho][Wo][3]; TMAE_RESIZE_F32_NCHW f32 [n][3][Ho][Wo] = v / 255 (ToTensor);
+ * TMAE_RESIZE_F32_NCHW_NORM (v / 255 - mean[c]) / std[c] (mean / std: 3 host floats each), bitwise torch's. */
+enum { TMAE_RESIZE_U8_HWC = 0, TMAE_RESIZE_F32_NCHW = 1, TMAE_RESIZE_F32_NCHW_NORM = 2 };
+long long tmae_resize_u8_workspace(int n, int H, int W, int Ho, int Wo); /* bytes (0 unless both passes run) */
+int tmae_resize_u8(const unsigned char* src, int n, int H, int W, int Ho, int Wo, const int* kk_h,
+                   const int* bounds_h, int ksize_h, const int* kk_v, const int* bounds_v, int ksize_v, int out_mode,
+                   const float* mean, const float* std, void* out, unsigned char* work, long long work_bytes,
+                   void* stream);
+/* uint8 RGB [npixels][3] -> gray [npixels] = (9798 R + 19235 G + 3735 B + 16384) >> 15: scores.imread_gray for
+ * non-JPEG files (cv2.imread IMREAD_GRAYSCALE through libpng), in front of tmae_image_scores */
+int tmae_rgb_to_gray_u8(const unsigned char* rgb, long long npixels, unsigned char* gray, void* stream);
+
 /* ---------------------------------------------------------------- VGG16 feature loss (MCM.forward_loss,
  * models/Compression/loss/vgg.py:86-115 with common/image_utils.py:4-23).  The convolutions are tmae_conv3x3
  * (act TMAE_ACT_RELU) and tmae_conv_dgrad; these are the glue kernels, NHWC, dtype = operand type. */

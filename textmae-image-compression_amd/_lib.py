@@ -177,6 +177,9 @@ SIGNATURES = {
     "tmae_huffman_decode": [ctypes.c_char_p, LL, P, P, P, I, P, LL, ctypes.POINTER(LL)],
     "tmae_image_metrics": [P, P, I, I, I, I, P, LL, P, P],
     "tmae_image_scores": [P, I, I, I, I, I, P, LL, P, P],
+    # model inputs: Pillow-exact resize and the score producer's grayscale (csrc/resize.hip)
+    "tmae_resize_u8": [P, I, I, I, I, I, P, P, I, P, P, I, I, ctypes.POINTER(F), ctypes.POINTER(F), P, P, LL, P],
+    "tmae_rgb_to_gray_u8": [P, LL, P, P],
     # VGG16 feature loss glue
     "tmae_vgg_prep": [P, I, I, I, I, I, P, I, P],
     "tmae_vgg_prep_bwd": [P, I, I, I, I, I, P, I, P],
@@ -223,6 +226,7 @@ VALUE_FUNCS = {"tmae_wgrad_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_wgrad_workspace_nb": ([I, I, I, I, I, I], ctypes.c_longlong),
                "tmae_metrics_workspace": ([I, I, I, I], ctypes.c_longlong),
                "tmae_image_scores_workspace": ([I, I, I, I], ctypes.c_longlong),
+               "tmae_resize_u8_workspace": ([I, I, I, I, I], ctypes.c_longlong),
                "tmae_qkv_attn_supported": ([I, I, I], ctypes.c_int),
                "tmae_gemm_force_tile": ([I], ctypes.c_int),
                "tmae_mha_force_stream": ([I], ctypes.c_int),

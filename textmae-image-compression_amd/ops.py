@@ -22,6 +22,7 @@ __all__ = [
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "rans_encode_lanes", "rans_decode_lanes",
+    "resize_tables", "resize_u8", "rgb_to_gray_u8",
     "mae_loss", "TMAE_F32", "TMAE_BF16", "ACT_NONE", "ACT_GELU",
 ]
 
@@ -726,4 +727,149 @@ def bpp(y_lik, z_lik, num_pixels):
     out = torch.empty((), dtype=torch.float32, device=y.device)
     _lib.call("tmae_bpp_sum", y.data_ptr(), y.numel(), z.data_ptr(), z.numel(), work.data_ptr(), out.data_ptr(),
               float(num_pixels), _stream())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- input pipeline
+# Pillow's 8-bit resample (ImagingResample, src/libImaging/Resample.c) is integer arithmetic over coefficient
+# tables computed in C doubles; the tables are rebuilt here with the same operations in the same order (Python
+# floats are C doubles), the device kernels (csrc/resize.hip) apply them.
+RESIZE_PRECISION_BITS = 32 - 8 - 2
+_RESIZE_FILTERS = {}
+_RESIZE_TABLES = {}
+_RESIZE_DEVICE_TABLES = {}
+
+
+def _bicubic_filter(x: float) -> float:
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _bilinear_filter(x: float) -> float:
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return 1.0 - x
+    return 0.0
+
+
+_RESIZE_FILTERS.update({"bicubic": (_bicubic_filter, 2.0), "bilinear": (_bilinear_filter, 1.0)})
+
+
+def resize_tables(in_size: int, out_size: int, filter: str = "bicubic"):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for one axis: (kk int32 [out_size][ksize] 22-bit fixed
+    point, bounds int32 [out_size][2] = (xmin, n)) as numpy arrays, cached per (in, out, filter).  Output xx is
+    clip8((2^21 + sum_{x < n} px[xmin + x] * kk[xx][x]) >> 22); entries past n are 0."""
+    import math
+
+    import numpy as np
+
+    key = (int(in_size), int(out_size), filter)
+    hit = _RESIZE_TABLES.get(key)
+    if hit is not None:
+        return hit
+    if filter not in _RESIZE_FILTERS:
+        raise ValueError(f"resize_tables: unknown filter {filter!r} (bicubic, bilinear)")
+    in_size, out_size = key[0], key[1]
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"resize_tables: sizes must be >= 1, got {in_size} -> {out_size}")
+    f, fsupport = _RESIZE_FILTERS[filter]
+    filterscale = scale = float(in_size) / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = fsupport * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    kk = np.zeros((out_size, ksize), dtype=np.int32)
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    one = float(1 << RESIZE_PRECISION_BITS)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = int(center - support + 0.5)
+        if xmin < 0:
+            xmin = 0
+        xmax = int(center + support + 0.5)
+        if xmax > in_size:
+            xmax = in_size
+        n = xmax - xmin
+        if not (0 <= xmin and n >= 1 and xmin + n <= in_size and n <= ksize):
+            raise ValueError(f"resize_tables: output {xx} of {in_size} -> {out_size} has taps [{xmin}, {xmin + n})")
+        w = [f((x + xmin - center + 0.5) * ss) for x in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        # int() truncates toward zero like the C cast
+        kk[xx, :n] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+        bounds[xx] = (xmin, n)
+    kk.setflags(write=False)
+    bounds.setflags(write=False)
+    _RESIZE_TABLES[key] = (kk, bounds)
+    return kk, bounds
+
+
+def _resize_device_tables(in_size, out_size, filter, device):
+    """device copies of one axis' tables: (kk, bounds, ksize)"""
+    key = (int(in_size), int(out_size), filter, torch.device(device))
+    hit = _RESIZE_DEVICE_TABLES.get(key)
+    if hit is None:
+        kk, bounds = resize_tables(in_size, out_size, filter)  # read-only cached arrays: upload writable copies
+        hit = (torch.from_numpy(kk.copy()).to(device), torch.from_numpy(bounds.copy()).to(device), kk.shape[1])
+        _RESIZE_DEVICE_TABLES[key] = hit
+    return hit
+
+
+_RESIZE_MODES = {"u8": 0, "f32": 1}
+
+
+def resize_u8(src, size, filter="bicubic", out="u8", mean=None, std=None):
+    """PIL.Image.resize of a batch on the device, bit for bit (csrc/resize.hip): src uint8 [n, H, W, 3] (or
+    [H, W, 3]), size an int or (h, w).  out="u8": uint8 [n, h, w, 3]; out="f32": f32 [n, 3, h, w] = v / 255
+    (ToTensor), or (v / 255 - mean) / std when mean and std are given (Normalize) -- bitwise torch's."""
+    single = src.dim() == 3
+    s = src.unsqueeze(0) if single else src
+    if s.dim() != 4 or s.shape[3] != 3:
+        raise ValueError(f"resize_u8: src must be uint8 [n, H, W, 3], got {tuple(src.shape)}")
+    s = _need(s.contiguous(), torch.uint8, "src")
+    if out not in _RESIZE_MODES:
+        raise ValueError(f"resize_u8: out must be 'u8' or 'f32', got {out!r}")
+    if (mean is None) != (std is None) or (mean is not None and out != "f32"):
+        raise ValueError("resize_u8: mean and std go together, with out='f32'")
+    Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    n, H, W = int(s.shape[0]), int(s.shape[1]), int(s.shape[2])
+    if min(n, H, W, Ho, Wo) < 1:
+        raise ValueError(f"resize_u8: sizes must be >= 1, got n={n} {H}x{W} -> {Ho}x{Wo}")
+    kh, bh, ksh = _resize_device_tables(W, Wo, filter, s.device)
+    kv, bv, ksv = _resize_device_tables(H, Ho, filter, s.device)
+    mode = _RESIZE_MODES[out] + (1 if mean is not None else 0)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean]) if mean is not None else None
+    sd = (ctypes.c_float * 3)(*[float(v) for v in std]) if std is not None else None
+    if out == "u8":
+        dst = torch.empty((n, Ho, Wo, 3), dtype=torch.uint8, device=s.device)
+    else:
+        dst = torch.empty((n, 3, Ho, Wo), dtype=torch.float32, device=s.device)
+    nwork = int(_lib.value("tmae_resize_u8_workspace", n, H, W, Ho, Wo))
+    work = torch.empty(nwork, dtype=torch.uint8, device=s.device) if nwork else None
+    with torch.cuda.device(s.device):
+        _lib.call("tmae_resize_u8", s.data_ptr(), n, H, W, Ho, Wo, kh.data_ptr(), bh.data_ptr(), ksh, kv.data_ptr(),
+                  bv.data_ptr(), ksv, mode, m, sd, dst.data_ptr(), _p(work), nwork, _stream())
+    return dst[0] if single else dst
+
+
+def rgb_to_gray_u8(src):
+    """uint8 [..., 3] (device) -> uint8 [...]: (9798 R + 19235 G + 3735 B + 16384) >> 15, the grayscale
+    scores.imread_gray computes on the host for non-JPEG files"""
+    if src.dim() < 2 or src.shape[-1] != 3 or src.numel() == 0:
+        raise ValueError(f"rgb_to_gray_u8: src must be uint8 [..., 3] and not empty, got {tuple(src.shape)}")
+    s = _need(src.contiguous(), torch.uint8, "src")
+    out = torch.empty(s.shape[:-1], dtype=torch.uint8, device=s.device)
+    with torch.cuda.device(s.device):
+        _lib.call("tmae_rgb_to_gray_u8", s.data_ptr(), out.numel(), out.data_ptr(), _stream())
     return out

@@ -62,17 +62,22 @@ def bits_per_pixel(strings, huffman_bits, num_pixels):
     return sum(len(s[0]) for s in strings) * 8.0 / num_pixels + len(huffman_bits) / num_pixels
 
 
-def save_output(x, ori_shape, file_name, output_dir):
-    """testing.py:52-57 (the resized image is discarded there too: the saved file is the 224^2 output)"""
+def save_output(x, ori_shape, file_name, output_dir, original_size=False):
+    """testing.py:52-57.  The reference resizes the output back to ``ori_shape`` and discards the result: the
+    saved file is the 224^2 output, and that stays the default.  With ``original_size`` the resize (PIL bicubic,
+    on the device: ops.resize_u8) is the image that is saved; ori_shape is PIL's (W, H)."""
     from PIL import Image
 
-    a = x.squeeze().clamp(0, 1).mul(255).round().byte().permute(1, 2, 0).cpu().numpy()
-    Image.fromarray(a).save(os.path.join(output_dir, file_name))
+    a = x.squeeze().clamp(0, 1).mul(255).round().byte().permute(1, 2, 0)
+    if original_size:
+        a = ops.resize_u8(a.contiguous(), (int(ori_shape[1]), int(ori_shape[0])))
+    Image.fromarray(a.cpu().numpy()).save(os.path.join(output_dir, file_name))
 
 
 @torch.no_grad()
-def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None, lanes=None):
-    """testing.py:60-100; lanes (--lanes N) codes through compress_batch / decompress_batch with N y lanes"""
+def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None, lanes=None, original_size=False):
+    """testing.py:60-100; lanes (--lanes N) codes through compress_batch / decompress_batch with N y lanes;
+    original_size (--original_size) saves the output resized back to ori_shape"""
     device = next(model.parameters()).device
     x = x.to(device)
     total_score = total_score.to(device)
@@ -95,7 +100,7 @@ def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None,
     num_pixels = x.size(0) * x.size(2) * x.size(3)
     bpp = bits_per_pixel(out_enc["string"], compressed_ids_keep, num_pixels)
     if output_dir is not None and file_name is not None:
-        save_output(out_dec["x_hat"], ori_shape, file_name, output_dir)
+        save_output(out_dec["x_hat"], ori_shape, file_name, output_dir, original_size)
     return {"psnr": metrics["psnr"], "ms-ssim": metrics["ms-ssim"], "bpp": bpp, "encoding_time": enc_time,
             "decoding_time": dec_time}
 
@@ -117,20 +122,27 @@ def inference_entropy_estimation(model, x, total_score):
             "decoding_time": elapsed / 2.0}
 
 
-def load_test_images(paths, size=224):
-    """the test transform (utils/dataloader.py:69-73): RGB, PIL bicubic resize to size^2, ToTensor"""
+def load_test_images(paths, size=224, device=None):
+    """the test transform (utils/dataloader.py:69-73): RGB, PIL bicubic resize to size^2, ToTensor.  With a
+    ``device`` the host only decodes: the uint8 image is uploaded and the resize + ToTensor run there
+    (ops.resize_u8, equal to the host path bit for bit); the tensors stay on that device."""
     from PIL import Image
 
     out = []
     for p in paths:
         im = Image.open(p).convert("RGB")
         ori = im.size
+        if device is not None:
+            x = torch.from_numpy(np.array(im)).to(device)
+            out.append((ops.resize_u8(x.unsqueeze(0), size, out="f32"), ori))
+            continue
         a = np.array(im.resize((size, size), Image.BICUBIC), dtype=np.float32) / 255.0
         out.append((torch.from_numpy(a).permute(2, 0, 1).unsqueeze(0).contiguous(), ori))
     return out
 
 
-def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False, lanes=None):
+def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False, lanes=None,
+               original_size=False):
     """testing.py:128-165 over pre-loaded (img [1,3,S,S], orig_shape) pairs and a [N, L] score tensor"""
     metrics = defaultdict(float)
     if output_dir is not None:
@@ -140,7 +152,8 @@ def eval_model(model, output_dir, images, scores, names=None, entropy_estimation
         if entropy_estimation:
             rv = inference_entropy_estimation(model, img, ts)
         else:
-            rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir, lanes=lanes)
+            rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir, lanes=lanes,
+                           original_size=original_size)
         for k, v in rv.items():
             metrics[k] += v
     for k in metrics:
@@ -176,6 +189,8 @@ def setup_args():
     p.add_argument("--input_size", type=int, default=224, required=True)
     p.add_argument("--lanes", type=int, default=None, choices=[1, 2, 4, 8, 16, 32, 64],
                    help="code on the device (compress_batch / decompress_batch) with this many interleaved y lanes")
+    p.add_argument("--original_size", action="store_true",
+                   help="save each output resized back to its image's original size (bicubic, on the device)")
     return p
 
 
@@ -201,7 +216,7 @@ def main(argv):
             model.compute_dtype = torch.bfloat16
         model.update(force=True)
         m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths], args.entropy_estimation,
-                       lanes=args.lanes)
+                       lanes=args.lanes, original_size=args.original_size)
         for k, v in m.items():
             results[k].append(v)
     desc = "entropy estimation" if args.entropy_estimation else args.entropy_coder

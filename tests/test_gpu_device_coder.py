@@ -112,8 +112,8 @@ class Case:
         from textmae_amd.coder import DeviceRansEncoder
 
         n, nseg, seg_len = self.shape
-        return DeviceRansEncoder().encode_streams(self.sym, self.sym_strides, self.idx, self.idx_strides, n, nseg,
-                                                  seg_len, self.tabs)
+        return DeviceRansEncoder().encode_records(self.sym, self.sym_strides, self.idx, self.idx_strides, n, nseg,
+                                                  seg_len, self.tabs, lanes=1)
 
     def decode(self, strings, calls, first_stream=0, nstreams=None):
         """decode `calls` = [(seg0, nseg), ...] -> symbols [stream][segment][seg_len] (numpy), status"""
@@ -122,10 +122,10 @@ class Case:
         n, nseg, seg_len = self.shape
         nstreams = n if nstreams is None else nstreams
         dec = DeviceRansDecoder()
-        dec.set_streams(strings, DEV)
+        dec.set_records(strings, 1, DEV)
         out = torch.full((nseg, n, seg_len), 7777, dtype=torch.int32, device=DEV)
         for seg0, ns in calls:
-            dec.decode_streams(first_stream, nstreams, self.idx[first_stream * self.idx_strides[1]:], self.idx_strides,
+            dec.decode_records(first_stream, nstreams, self.idx[first_stream * self.idx_strides[1]:], self.idx_strides,
                                out.view(-1)[first_stream * self.sym_strides[1]:], self.sym_strides, seg0, ns, seg_len,
                                self.tabs)
         return out.cpu().numpy().transpose(1, 0, 2), dec.status()

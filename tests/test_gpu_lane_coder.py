@@ -172,13 +172,14 @@ def test_encode_records_equal_host_coder(case1, lanes):
 
 
 def test_one_lane_through_the_lanes_entry(case1):
-    """test 2: lanes = 1 through rans_encode_lanes / rans_decode_lanes is encode_streams' format"""
+    """test 2: lanes = 1 through rans_encode_lanes / rans_decode_lanes is the format of encode_records(lanes=1),
+    which takes the wave-per-stream kernel"""
     from textmae_amd import ops
     from textmae_amd.coder import DeviceRansEncoder
 
     n, nseg, seg_len = case1.shape
-    plain = DeviceRansEncoder().encode_streams(case1.sym, case1.sym_strides, case1.idx, case1.idx_strides, n, nseg,
-                                               seg_len, case1.tabs)
+    plain = DeviceRansEncoder().encode_records(case1.sym, case1.sym_strides, case1.idx, case1.idx_strides, n, nseg,
+                                               seg_len, case1.tabs, lanes=1)
     assert plain == case1.want(1)
     cap = ops.rans_stream_cap_words(nseg * seg_len)
     slabs = torch.zeros((n, cap), dtype=torch.int32, device=DEV)
@@ -232,6 +233,32 @@ def test_resumed_decode(case1, lanes):
     got, status = case1.decode(want, lanes, [(0, 3)], first=1, count=1)
     assert not status.any() and np.array_equal(got[1], case1.sym_h[1])
     assert (got[0] == FILL).all() and (got[2] == FILL).all()  # the other streams' outputs are untouched
+
+
+def test_mixed_lane_counts_in_one_decoder(gc):
+    """test 5b: one decoder holds records of 1, 1, 4 and 4 lanes (2 segments of 67 symbols: ragged over the 64-symbol
+    chunk and over four lanes); each group is decoded by its own call, by its own kernel, to what decode_record
+    returns for the same records"""
+    from textmae_amd.coder import DeviceRansDecoder, decode_record
+
+    c = Case(gc, 4, 2, 67, seed=77)
+    n, nseg, seg_len = c.shape
+    lanes = [1, 1, 4, 4]
+    records = c.want(1)[:2] + c.want(4)[2:]
+    dec = DeviceRansDecoder()
+    dec.set_records(records, lanes, DEV)
+    out = torch.full((nseg, n, seg_len), FILL, dtype=torch.int32, device=DEV)
+    for first in (0, 2):
+        dec.decode_records(first, 2, c.idx[first * c.idx_strides[1]:], c.idx_strides,
+                           out.view(-1)[first * c.sym_strides[1]:], c.sym_strides, 0, nseg, seg_len, c.tabs)
+    got = out.cpu().numpy().transpose(1, 0, 2)
+    assert not dec.status().any()
+    for b in range(n):
+        want = decode_record(records[b], c.idx_h[b], nseg, seg_len, lanes[b], c.tabs_h)
+        assert np.array_equal(got[b].reshape(-1), want), f"record {b}"
+        assert np.array_equal(want, c.sym_h[b].reshape(-1))
+    with pytest.raises(ValueError, match="one lane count"):
+        dec.decode_records(1, 2, c.idx, c.idx_strides, out.view(-1), c.sym_strides, 0, nseg, seg_len, c.tabs)
 
 
 @pytest.mark.parametrize("hw", [1, 9])

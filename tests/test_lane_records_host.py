@@ -164,6 +164,42 @@ def test_parse_record_rejects_malformed_headers(coder, data):
         coder.decode_record(words[1:].tobytes(), idx, NSEG, SEG_LEN, lanes, tabs)
 
 
+def test_set_records_tables_on_the_host(coder, data):
+    """DeviceRansDecoder.set_records with device="cpu": records of one lane are their own sub-streams (offsets 0, 2, 5
+    and counts 2, 3, 5 for 8, 12 and 20 bytes, the words concatenated), a record with lanes points past its header,
+    and a bad header is reported in the caller's words"""
+    rng = np.random.default_rng(5)
+    strings = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (8, 12, 20)]
+    dec = coder.DeviceRansDecoder()
+    dec.set_records(strings, 1, "cpu")
+    assert dec._woff.dtype == torch.int64 and dec._woff.tolist() == [0, 2, 5]
+    assert dec._wlen.dtype == torch.int32 and dec._wlen.tolist() == [2, 3, 5]
+    assert dec._words.dtype == torch.int32 and dec._words.numpy().tobytes() == b"".join(strings)
+    assert dec._total == 10 and dec._state.numel() == dec._pos.numel() == dec._status.numel() == 3
+
+    sym, idx, tabs = data
+    rec = coder.encode_record(sym, idx, NSEG, SEG_LEN, 4, tabs)
+    o4, c4 = coder.parse_record(rec, 4)
+    assert o4[0] == 5
+    dec.set_records([strings[1], rec], [1, 4], "cpu")
+    assert dec._woff.tolist() == [0] + (3 + o4).tolist() and dec._woff[1] == 3 + 5  # past the 5-word header
+    assert dec._wlen.tolist() == [3] + c4.tolist()
+    assert dec._words.numpy().tobytes() == strings[1] + rec
+    assert dec._state.numel() == dec._pos.numel() == 5 and dec._status.numel() == 2
+
+    names = ["y stream of image 0", "z stream of image 0"]
+    w = np.frombuffer(rec, dtype="<u4").copy()
+    w[0] = 2
+    with pytest.raises(ValueError, match="^z stream of image 0: record header says 2 lanes, 4 expected"):
+        dec.set_records([strings[1], w.tobytes()], [1, 4], "cpu", what=names)
+    with pytest.raises(ValueError, match="^record 1: record header says 2 lanes, 4 expected"):
+        dec.set_records([strings[1], w.tobytes()], [1, 4], "cpu")
+    with pytest.raises(ValueError, match="^y stream of image 0: a stream is at least 8 bytes"):
+        dec.set_records([strings[0][:4], rec], [1, 4], "cpu", what=names)
+    with pytest.raises(ValueError, match="set_records\\(\\) first"):
+        coder.DeviceRansDecoder().decode_records(0, 1, None, (0, 0), None, (0, 0), 0, 1, 1, None)
+
+
 def enc_call(ops, lanes=4, nstreams=2, cap=16, slabs=None, nwords=None, status=None):
     i32 = lambda n: torch.zeros(n, dtype=torch.int32)  # noqa: E731  (host tensors: validation comes first)
     tabs = (i32(8).view(2, 4), i32(2), i32(2))

@@ -6,12 +6,13 @@ EntropyModel.compress) and ``pmf_to_quantized_cdf`` (EntropyModel._pmf_to_cdf). 
 Python lists (the reference passes ``.tolist()`` results), numpy arrays or CPU tensors; symbol
 arrays are handed to the coder without per-element Python work.
 
-``DeviceRansEncoder`` / ``DeviceRansDecoder`` code the same format on the GPU (csrc/rans_device.hip), many
-independent streams at once from and to device tensors: the coder of ``MCM.compress_batch`` / ``decompress_batch``.
-
 ``encode_record`` / ``decode_record`` / ``parse_record`` are the host side of the lane-interleaved records
 (``compress_batch(lanes=L)``): a record is ``lanes`` ordinary streams behind a small header, each stream what
-``RansEncoder`` writes for that lane's share of the symbols.
+``RansEncoder`` writes for that lane's share of the symbols; one lane is the plain stream without a header.
+
+``DeviceRansEncoder.encode_records`` / ``DeviceRansDecoder.set_records`` + ``decode_records`` code those records on
+the GPU (csrc/rans_device.hip), many at once from and to device tensors: the coder of ``MCM.compress_batch`` /
+``decompress_batch``.
 """
 from __future__ import annotations
 
@@ -145,9 +146,9 @@ class RansDecoder:
 EMPTY_STREAM = bytes([0, 0, 0, 0x80, 0, 0, 0, 0])  # the coder's flush of state 2^31: a sub-stream without symbols
 
 
-def check_lanes(lanes) -> int:
+def check_lanes(lanes, who="") -> int:
     if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or int(lanes) not in (1, 2, 4, 8, 16, 32, 64):
-        raise ValueError(f"lanes = {lanes!r} must be a power of two in 1..64")
+        raise ValueError(f"{who}lanes = {lanes!r} must be a power of two in 1..64")
     return int(lanes)
 
 
@@ -212,8 +213,9 @@ def decode_record(record, indexes, nseg: int, seg_len: int, lanes: int, tables) 
     return out.reshape(-1)
 
 
-# ------------------------------------------------------------------ per-image streams coded on the device
-# (csrc/rans_device.hip): the same format as the classes above, one independent stream per image, one wave each.
+# ------------------------------------------------------------------ records coded on the device
+# (csrc/rans_device.hip): the same format as the classes above, one independent record per image.  A record of one
+# lane is the plain stream and takes the wave-per-stream kernels; more lanes take the thread-per-sub-stream kernels.
 STREAM_STATUS = {1: "output buffer too small", 2: "corrupt stream (symbol outside its CDF row)",
                  3: "corrupt stream (escape longer than 8 digits)", 4: "stream exhausted",
                  5: "CDF index outside the tables", 6: "stream outside the word buffer"}
@@ -228,165 +230,97 @@ def _raise_status(status, what):
 
 
 class DeviceRansEncoder:
-    """Device symbols and indexes plus a layout in, one rANS string per stream out.  Stream b is what
-    RansEncoder.encode_with_indexes returns for stream b's symbols in coding order."""
+    """Device symbols and indexes plus a layout in, one record per stream out: record b is what encode_record
+    returns for stream b's symbols in coding order (at one lane, RansEncoder.encode_with_indexes' string)."""
 
     def __init__(self):
         self._bufs = {}
 
-    def _buffers(self, device, nstreams, cap):
-        key = (device, nstreams, cap)
-        bufs = self._bufs.get(key)
-        if bufs is None:
-            slabs = torch.empty((nstreams, cap), dtype=torch.int32, device=device)
-            dense = torch.empty(nstreams * cap, dtype=torch.int32, device=device)
-            # one small D2H: int64 word offsets [nstreams + 1] | int32 nwords [nstreams] | int32 status [nstreams]
-            meta = torch.empty(4 * nstreams + 2, dtype=torch.int32, device=device)
-            bufs = self._bufs[key] = (slabs, dense, meta)
-        return bufs
-
-    def encode_streams(self, symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables,
-                       what="stream") -> list:
-        """stream b codes segments j = 0..nseg-1, each seg_len int32 at base + j * strides[0] + b * strides[1]
-        (elements); tables = EntropyModel.device_tables().  Synchronises: the strings are host bytes."""
-        from . import ops
-
-        cap = ops.rans_stream_cap_words(nseg * seg_len)
-        slabs, dense, meta = self._buffers(symbols.device, nstreams, cap)
-        offs = meta[:2 * nstreams + 2].view(torch.int64)
-        nwords, status = meta[2 * nstreams + 2:3 * nstreams + 2], meta[3 * nstreams + 2:]
-        ops.rans_encode_streams(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap,
-                                nwords, status)
-        ops.rans_pack_streams(slabs, cap, nwords, nstreams, dense, dense.numel(), offs, status)
-        meta_h = meta.cpu().numpy()
-        offs_h = meta_h[:2 * nstreams + 2].view(np.int64)
-        nw_h, st_h = meta_h[2 * nstreams + 2:3 * nstreams + 2], meta_h[3 * nstreams + 2:]
-        _raise_status(st_h, what)
-        raw = dense[:int(offs_h[nstreams])].cpu().numpy().tobytes()  # payload-sized copy
-        return [raw[4 * int(offs_h[b]):4 * (int(offs_h[b]) + int(nw_h[b]))] for b in range(nstreams)]
-
-
-    def _lane_buffers(self, device, nstreams, lanes, cap):
+    def _buffers(self, device, nstreams, lanes, cap):
         key = (device, nstreams, lanes, cap)
         bufs = self._bufs.get(key)
         if bufs is None:
             nsub = nstreams * lanes
             slabs = torch.empty((nsub, cap), dtype=torch.int32, device=device)
             dense = torch.empty(nsub * cap, dtype=torch.int32, device=device)
-            # one small D2H: int64 word offsets [nsub + 1] | int32 nwords [nsub] | pack status [nsub] | status [nstreams]
-            meta = torch.empty(4 * nsub + 2 + nstreams, dtype=torch.int32, device=device)
+            # one small D2H: int64 word offsets [nsub + 1] | int32 nwords [nsub] | status [nstreams] | pack status
+            # [nsub], the last only for lanes > 1 (at one lane pack reports into the streams' own status words)
+            meta = torch.empty(3 * nsub + 2 + nstreams + (nsub if lanes > 1 else 0), dtype=torch.int32, device=device)
             bufs = self._bufs[key] = (slabs, dense, meta)
         return bufs
 
-    def encode_records(self, symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, lanes,
+    def encode_records(self, symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, lanes=1,
                        what="stream") -> list:
-        """encode_streams with every stream dealt over `lanes` sub-streams: one record (see encode_record) per
-        stream.  lanes = 1 is encode_streams itself.  The sub-streams are packed stream-major, lane-minor, so a
-        record's payload is one slice of the dense buffer; its header comes from the word counts on the host."""
+        """stream b codes segments j = 0..nseg-1, each seg_len int32 at base + j * strides[0] + b * strides[1]
+        (elements), dealt over `lanes` sub-streams; tables = EntropyModel.device_tables().  The sub-streams are packed
+        stream-major, lane-minor, so a record's payload is one slice of the dense buffer; its header (none at one
+        lane) comes from the word counts on the host.  Synchronises: the records are host bytes."""
         from . import ops
 
         lanes = check_lanes(lanes)
-        if lanes == 1:
-            return self.encode_streams(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, what)
         nsub = nstreams * lanes
         cap = ops.rans_stream_cap_words(nseg * ((seg_len + lanes - 1) // lanes))
-        slabs, dense, meta = self._lane_buffers(symbols.device, nstreams, lanes, cap)
-        offs = meta[:2 * nsub + 2].view(torch.int64)
-        nwords, pstatus, status = meta[2 * nsub + 2:3 * nsub + 2], meta[3 * nsub + 2:4 * nsub + 2], meta[4 * nsub + 2:]
-        pstatus.zero_()
-        ops.rans_encode_lanes(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap,
-                              nwords, status, lanes)
+        slabs, dense, meta = self._buffers(symbols.device, nstreams, lanes, cap)
+        o, s = 2 * nsub + 2, 3 * nsub + 2
+        offs, nwords, status, pstatus = meta[:o].view(torch.int64), meta[o:s], meta[s:s + nstreams], meta[s + nstreams:]
+        args = (symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap, nwords, status)
+        if lanes == 1:
+            ops.rans_encode_streams(*args)
+            pstatus = status
+        else:
+            pstatus.zero_()
+            ops.rans_encode_lanes(*args, lanes)
         ops.rans_pack_streams(slabs, cap, nwords, nsub, dense, dense.numel(), offs, pstatus)
         meta_h = meta.cpu().numpy()
-        offs_h = meta_h[:2 * nsub + 2].view(np.int64)
-        nw_h = meta_h[2 * nsub + 2:3 * nsub + 2].reshape(nstreams, lanes)
-        st_h = np.maximum(meta_h[4 * nsub + 2:], meta_h[3 * nsub + 2:4 * nsub + 2].reshape(nstreams, lanes).max(axis=1))
+        offs_h, nw_h = meta_h[:o].view(np.int64), meta_h[o:s].reshape(nstreams, lanes)
+        st_h = meta_h[s:s + nstreams]
+        if lanes > 1:
+            st_h = np.maximum(st_h, meta_h[s + nstreams:].reshape(nstreams, lanes).max(axis=1))
         _raise_status(st_h, what)
         raw = dense[:int(offs_h[nsub])].cpu().numpy().tobytes()  # payload-sized copy
+        cut = (4 * offs_h[::lanes]).tolist()  # a status-free record's sub-streams are contiguous in the dense buffer
+        if lanes == 1:
+            return [raw[cut[b]:cut[b + 1]] for b in range(nstreams)]
         head = np.concatenate([np.full((nstreams, 1), lanes, dtype=np.int32), nw_h], axis=1).astype("<u4")
-        return [head[b].tobytes() + raw[4 * int(offs_h[b * lanes]):4 * int(offs_h[(b + 1) * lanes])]
-                for b in range(nstreams)]
+        return [head[b].tobytes() + raw[cut[b]:cut[b + 1]] for b in range(nstreams)]
 
 
 class DeviceRansDecoder:
-    """set_streams uploads every string with ONE H2D copy; decode_streams then maps device indexes to device
-    symbols, any number of times per stream (each call carries on where the last one stopped), without touching
-    the host; check() reads the status words (the only synchronisation).  set_records / decode_records are the same
-    for lane-interleaved records (one status word per record)."""
+    """set_records uploads every record with ONE H2D copy; decode_records then maps device indexes to device
+    symbols, any number of times per record (each call carries on where the last one stopped), without touching
+    the host; status() reads the status words, one per record (the only synchronisation)."""
 
     def __init__(self):
         self._n = 0
-        self._lanes = None  # per-record lane counts after set_records
 
-    def set_streams(self, strings, device):
-        n = len(strings)
-        if n == 0:
-            raise ValueError("DeviceRansDecoder: no streams")
-        lens = np.empty(n, dtype=np.int32)
-        for i, s in enumerate(strings):
-            if len(s) < 8 or len(s) % 4:
-                raise ValueError(f"stream {i}: a stream is a whole number of 32-bit words, >= 8 bytes (got {len(s)})")
-            lens[i] = len(s) // 4
-        offs = np.zeros(n, dtype=np.int64)
-        np.cumsum(lens[:-1], out=offs[1:])
-        total = int(offs[-1]) + int(lens[-1])
-        hdr = (12 * n + 7) // 8 * 8
-        buf = np.zeros(hdr + 4 * total, dtype=np.uint8)
-        buf[:8 * n] = offs.view(np.uint8)
-        buf[8 * n:12 * n] = lens.view(np.uint8)
-        buf[hdr:] = np.frombuffer(b"".join(bytes(s) for s in strings), dtype=np.uint8)
-        dev = torch.from_numpy(buf).to(device)  # the one upload
-        self._woff = dev[:8 * n].view(torch.int64)
-        self._wlen = dev[8 * n:12 * n].view(torch.int32)
-        self._words = dev[hdr:].view(torch.int32)
-        self._total = total
-        self._state = torch.zeros(n, dtype=torch.int64, device=device)
-        self._pos = torch.zeros(n, dtype=torch.int32, device=device)
-        self._status = torch.zeros(n, dtype=torch.int32, device=device)
-        self._started = np.zeros(n, dtype=bool)
-        self._lanes = None
-        self._n = n
-
-    def decode_streams(self, first_stream, nstreams, indexes, idx_strides, symbols, sym_strides, seg0, nseg, seg_len,
-                       tables):
-        """the next nseg segments of streams [first_stream, first_stream + nstreams): segment seg0 + j of stream b
-        is seg_len int32 at base + (seg0 + j) * strides[0] + b * strides[1]; symbols are written, indexes read"""
-        from . import ops
-
-        s0, s1 = int(first_stream), int(first_stream) + int(nstreams)
-        if self._n == 0 or self._lanes is not None:
-            raise ValueError("DeviceRansDecoder: set_streams() first")
-        if not (0 <= s0 < s1 <= self._n):
-            raise ValueError(f"streams [{s0}, {s1}) outside the {self._n} set")
-        started = self._started[s0:s1]
-        if started.any() != started.all():
-            raise ValueError("DeviceRansDecoder: streams of one call must have been decoded equally far")
-        ops.rans_decode_streams(self._words, self._total, self._woff[s0:s1], self._wlen[s0:s1], indexes, idx_strides,
-                                symbols, sym_strides, s1 - s0, seg0, nseg, seg_len, tables, self._state[s0:s1],
-                                self._pos[s0:s1], self._status[s0:s1], not started.any())
-        self._started[s0:s1] = True
-
-    def set_records(self, strings, lanes, device, what="record"):
-        """set_streams for lane-interleaved records: lanes is one lane count for every record or one per record.
-        The headers are parsed on the host (ValueError naming the record), the records go up whole in ONE copy, and
-        the sub-stream table points past the headers."""
+    def set_records(self, strings, lanes=1, device="cuda", what="record"):
+        """lanes is one lane count for every record or one per record; what names record i in an error, as
+        f"{what} {i}" or, given a sequence, as what[i].  The headers are parsed on the host, the records go up whole in
+        ONE copy, and the sub-stream table points past the headers (a record of one lane is its own sub-stream)."""
         n = len(strings)
         if n == 0:
             raise ValueError("DeviceRansDecoder: no records")
-        lanes = [check_lanes(lanes)] * n if isinstance(lanes, (int, np.integer)) else [check_lanes(v) for v in lanes]
-        if len(lanes) != n:
-            raise ValueError(f"{n} records but {len(lanes)} lane counts")
-        offs, lens, base = [], [], 0
-        for i, (s, L) in enumerate(zip(strings, lanes)):
+        if isinstance(lanes, (int, np.integer)):
+            lanes = np.full(n, check_lanes(lanes), dtype=np.int64)
+        else:
+            lanes = np.array([check_lanes(v) for v in lanes], dtype=np.int64)
+        if lanes.size != n:
+            raise ValueError(f"{n} records but {lanes.size} lane counts")
+        nbytes = np.fromiter(map(len, strings), dtype=np.int64, count=n)
+        base = np.zeros(n + 1, dtype=np.int64)  # first word of every record, then the total
+        np.cumsum(nbytes // 4, out=base[1:])
+        sub0 = np.zeros(n + 1, dtype=np.int64)  # first sub-stream of every record
+        np.cumsum(lanes, out=sub0[1:])
+        nsub, total = int(sub0[n]), int(base[n])
+        offs, lens = np.empty(nsub, dtype=np.int64), np.empty(nsub, dtype=np.int32)
+        offs[sub0[:n]], lens[sub0[:n]] = base[:n], nbytes // 4  # right as it stands for the records of one lane
+        for i in np.flatnonzero((lanes > 1) | (nbytes < 8) | (nbytes % 4 != 0)):  # the others have a header to parse
             try:
-                o, c = parse_record(s, L)
+                o, c = parse_record(strings[i], int(lanes[i]))
             except ValueError as e:
-                raise ValueError(f"{what} {i}: {e}") from None
-            offs.append(o + base)
-            lens.append(c)
-            base += len(s) // 4
-        offs, lens = np.concatenate(offs), np.concatenate(lens)
-        nsub, total = offs.size, base
+                name = f"{what} {i}" if isinstance(what, str) else what[i]
+                raise ValueError(f"{name}: {e}") from None
+            offs[sub0[i]:sub0[i + 1]], lens[sub0[i]:sub0[i + 1]] = o + base[i], c
         hdr = (12 * nsub + 7) // 8 * 8
         buf = np.zeros(hdr + 4 * total, dtype=np.uint8)
         buf[:8 * nsub] = offs.view(np.uint8)
@@ -401,18 +335,18 @@ class DeviceRansDecoder:
         self._pos = torch.zeros(nsub, dtype=torch.int32, device=device)
         self._status = torch.zeros(n, dtype=torch.int32, device=device)
         self._started = np.zeros(n, dtype=bool)
-        self._lanes = np.array(lanes, dtype=np.int64)
-        self._sub0 = np.concatenate([[0], np.cumsum(self._lanes)])  # first sub-stream of every record
+        self._lanes, self._sub0 = lanes, sub0
         self._n = n
 
     def decode_records(self, first_record, nrecords, indexes, idx_strides, symbols, sym_strides, seg0, nseg, seg_len,
                        tables):
-        """decode_streams for records [first_record, first_record + nrecords) of set_records, which must share one
-        lane count; records of one lane are plain streams and take decode_streams' kernel"""
+        """the next nseg segments of records [first_record, first_record + nrecords), which must share one lane count:
+        segment seg0 + j of record b is seg_len int32 at base + (seg0 + j) * strides[0] + b * strides[1]; symbols are
+        written, indexes read"""
         from . import ops
 
         r0, r1 = int(first_record), int(first_record) + int(nrecords)
-        if self._n == 0 or getattr(self, "_lanes", None) is None:
+        if self._n == 0:
             raise ValueError("DeviceRansDecoder: set_records() first")
         if not (0 <= r0 < r1 <= self._n):
             raise ValueError(f"records [{r0}, {r1}) outside the {self._n} set")
@@ -433,5 +367,5 @@ class DeviceRansDecoder:
         self._started[r0:r1] = True
 
     def status(self) -> np.ndarray:
-        """per-stream status words (synchronises)"""
+        """per-record status words (synchronises)"""
         return self._status.cpu().numpy()

@@ -44,28 +44,66 @@ __device__ __forceinline__ int bcast_i(int v, int lane) {
 __device__ __forceinline__ uint32_t bcast_u(uint32_t v, int lane) { return (uint32_t)bcast_i((int)v, lane); }
 
 // ------------------------------------------------------------------------------------------------ encode
+// The arithmetic of the format lives in the helpers of this section and of "decode" below; the wave-per-stream
+// kernels and the thread-per-sub-stream kernels ("lanes") differ in schedule only and both call them.
 struct EncState {
   uint64_t x;
   long long head;  // words [head, cap) of the slab are written
   int st;
 };
 
-__device__ __forceinline__ void enc_emit(EncState& e, uint32_t* __restrict__ slab, int lane) {
+// `store`: this thread writes the word (lane 0 of a wave that shares one state, every thread that owns its state)
+__device__ __forceinline__ void enc_emit(EncState& e, uint32_t* __restrict__ slab, bool store) {
   if (e.head <= 0) {  // the slab is full: stop this stream, never write outside it
     e.st = kStOverflow;
     return;
   }
   --e.head;
-  if (lane == 0) slab[e.head] = (uint32_t)e.x;
+  if (store) slab[e.head] = (uint32_t)e.x;
   e.x >>= 32;
 }
 
 // raw bits: freq = 2^12 of 2^16, so x_max = 2^12 << 47
-__device__ __forceinline__ void enc_put_bits(EncState& e, uint32_t* __restrict__ slab, int lane, uint32_t val) {
+__device__ __forceinline__ void enc_put_bits(EncState& e, uint32_t* __restrict__ slab, bool store, uint32_t val) {
   if (e.st) return;
-  if (e.x >= (1ull << 59)) enc_emit(e, slab, lane);
+  if (e.x >= (1ull << 59)) enc_emit(e, slab, store);
   if (e.st) return;
   e.x = (e.x << 4) | val;
+}
+
+// the 8-byte state flush: high word first (the buffer grows downward), so the stream starts with the low word
+__device__ __forceinline__ void enc_flush(EncState& e, uint32_t* __restrict__ slab, bool store) {
+  if (e.st == 0 && e.head < 2) e.st = kStOverflow;
+  if (e.st) return;
+  e.head -= 2;
+  if (store) {
+    slab[e.head + 1] = (uint32_t)(e.x >> 32);
+    slab[e.head] = (uint32_t)e.x;
+  }
+}
+
+// stage C: a symbol v of a row (offset, size entries) -> the value coded through the row; outside [0, size - 2) it is
+// the row's last symbol with raw = 2|v|-1 (below) or 2(v - max) (above) in ndig nibbles (up to the top non-zero one)
+struct EncValue {
+  int value;
+  uint32_t raw, esc, ndig;
+};
+
+__device__ __forceinline__ EncValue enc_clamp_escape(int v, int off, int size) {
+  const int max_value = size - 2;
+  EncValue r{(int)((uint32_t)v - (uint32_t)off), 0u, 0u, 0u};
+  if (r.value < 0) {
+    r.raw = (uint32_t)(-2 * (long long)r.value - 1);
+    r.value = max_value;
+  } else if (r.value >= max_value) {
+    r.raw = (uint32_t)(2 * (long long)(r.value - max_value));
+    r.value = max_value;
+  }
+  if (r.value == max_value) {
+    r.esc = 1;
+    r.ndig = r.raw ? 8u - ((uint32_t)__clz((int)r.raw) >> 2) : 0u;
+  }
+  return r;
 }
 
 // exact reciprocal of freq in [2, 2^16) (ryg_rans Rans64EncSymbolInit): floor(x / freq) = mulhi(x, rcp) >> shift for
@@ -80,6 +118,29 @@ __device__ __forceinline__ uint64_t enc_reciprocal(uint32_t freq, uint32_t& shif
   const uint32_t q4 = ((r3 << 16) + (freq - 1)) / freq;
   shift = bits - 1;
   return ((((uint64_t)q1 << 16) + q2) << 32) + (((uint64_t)q3 << 16) + q4);
+}
+
+// stage D: the fields of the put step from a symbol's two cdf entries
+struct EncSymbol {
+  uint64_t rcp;
+  uint32_t freq, shift, bias;
+};
+
+__device__ __forceinline__ EncSymbol enc_symbol(uint32_t start, uint32_t next) {
+  EncSymbol s{~0ull, next - start, 0u, start + (1u << 16) - 1};  // freq 1: q = x - 1, so x + bias + q (2^16 - 1) =
+  if (s.freq >= 2) {                                             // (x << 16) + start
+    s.rcp = enc_reciprocal(s.freq, s.shift);
+    s.bias = start;
+  }
+  return s;
+}
+
+// the put step: a state x >= freq << 47 stores a word first, then x += bias + floor(x / freq) (2^16 - freq)
+__device__ __forceinline__ bool enc_must_emit(uint64_t x, uint32_t freq) { return (uint32_t)(x >> 32) >= (freq << 15); }
+
+__device__ __forceinline__ uint64_t enc_put(uint64_t x, uint32_t freq, uint32_t shift, uint64_t rcp, uint32_t bias) {
+  const uint64_t q = __umul64hi(x, rcp) >> shift;
+  return x + bias + q * (uint64_t)((1u << 16) - freq);
 }
 
 __global__ void __launch_bounds__(kWave)
@@ -106,42 +167,22 @@ rans_encode_streams_kernel(const int* __restrict__ sym, long long sym_ss, long l
     uint32_t d_rcp_lo = 0, d_rcp_hi = 0, d_bias = 0, d_meta = 0, d_raw = c_raw;
     bool d_bad = false;
     if (t >= 3) {
-      const uint32_t freq = c_next - c_start;
-      uint32_t shift = 0;
-      uint64_t rcp = ~0ull;
-      d_bias = c_start + (1u << 16) - 1;  // freq 1: q = x - 1, so x + bias + q (2^16 - 1) = (x << 16) + start
-      if (freq >= 2) {
-        rcp = enc_reciprocal(freq, shift);
-        d_bias = c_start;
-      }
-      d_rcp_lo = (uint32_t)rcp;
-      d_rcp_hi = (uint32_t)(rcp >> 32);
+      const EncSymbol s = enc_symbol(c_start, c_next);
+      d_bias = s.bias;
+      d_rcp_lo = (uint32_t)s.rcp;
+      d_rcp_hi = (uint32_t)(s.rcp >> 32);
       // meta = freq (17 bits) | shift << 17 (5 bits) | escaped << 22 | ndig << 23
-      d_meta = freq | (shift << 17) | ((c_flags & 1u) << 22) | (((c_flags >> 1) & 15u) << 23);
+      d_meta = s.freq | (s.shift << 17) | ((c_flags & 1u) << 22) | (((c_flags >> 1) & 15u) << 23);
       d_bad = (c_flags >> 8) & 1u;
     }
     // ---- C: clamp and escape the value, issue the loads of cdf[value] and cdf[value + 1]
     if (t >= 2 && t < nchunks + 2) {
-      const int max_value = b_size - 2;
-      int value = (int)((uint32_t)b_v - (uint32_t)b_off);
-      uint32_t raw = 0, esc = 0, ndig = 0;
-      if (value < 0) {
-        raw = (uint32_t)(-2 * (long long)value - 1);
-        value = max_value;
-      } else if (value >= max_value) {
-        raw = (uint32_t)(2 * (long long)(value - max_value));
-        value = max_value;
-      }
-      if (value == max_value) {
-        esc = 1;
-#pragma unroll
-        for (int d = 0; d < 8; ++d) ndig += (raw >> (4 * d)) != 0 ? 1 : 0;  // nibbles up to the top non-zero one
-      }
+      const EncValue v = enc_clamp_escape(b_v, b_off, b_size);
       const int* __restrict__ row = cdfs + (size_t)b_ci * cdf_stride;
-      c_start = (uint32_t)row[value];
-      c_next = (uint32_t)row[value + 1];
-      c_raw = raw;
-      c_flags = esc | (ndig << 1) | (b_bad ? 1u << 8 : 0u);
+      c_start = (uint32_t)row[v.value];
+      c_next = (uint32_t)row[v.value + 1];
+      c_raw = v.raw;
+      c_flags = v.esc | (v.ndig << 1) | (b_bad ? 1u << 8 : 0u);
     }
     // ---- B: the row's size and offset (lanes past the end of the stream code nothing: row 0, never walked)
     if (t >= 1 && t < nchunks + 1) {
@@ -176,28 +217,19 @@ rans_encode_streams_kernel(const int* __restrict__ sym, long long sym_ss, long l
         const uint32_t r = bcast_u(d_raw, k);
         const int ndig = (int)(m >> 23);
         for (int d = 7; d >= 0; --d)
-          if (d < ndig) enc_put_bits(e, slab, lane, (r >> (4 * d)) & 15u);
-        enc_put_bits(e, slab, lane, (uint32_t)ndig);
+          if (d < ndig) enc_put_bits(e, slab, lane == 0, (r >> (4 * d)) & 15u);
+        enc_put_bits(e, slab, lane == 0, (uint32_t)ndig);
         if (e.st) break;
       }
-      if ((uint32_t)(e.x >> 32) >= (freq << 15)) {  // x >= freq << 47
-        enc_emit(e, slab, lane);
+      if (enc_must_emit(e.x, freq)) {
+        enc_emit(e, slab, lane == 0);
         if (e.st) break;
       }
       const uint64_t rcp = (uint64_t)bcast_u(d_rcp_lo, k) | ((uint64_t)bcast_u(d_rcp_hi, k) << 32);
-      const uint64_t q = __umul64hi(e.x, rcp) >> shift;
-      e.x = e.x + bcast_u(d_bias, k) + q * (uint64_t)((1u << 16) - freq);
+      e.x = enc_put(e.x, freq, shift, rcp, bcast_u(d_bias, k));
     }
   }
-  // 8-byte state flush: high word first (the buffer grows downward), so the stream starts with the low word
-  if (e.st == 0 && e.head < 2) e.st = kStOverflow;
-  if (e.st == 0) {
-    e.head -= 2;
-    if (lane == 0) {
-      slab[e.head + 1] = (uint32_t)(e.x >> 32);
-      slab[e.head] = (uint32_t)e.x;
-    }
-  }
+  enc_flush(e, slab, lane == 0);
   if (lane == 0) {
     nwords[b] = e.st ? 0 : (int)(cap - e.head);
     status[b] = e.st;
@@ -260,11 +292,93 @@ __device__ __forceinline__ uint32_t dec_next_word(DecState& d, const uint32_t* _
   return bcast_u(d.wbuf, r);
 }
 
-__device__ __forceinline__ uint32_t dec_get_bits4(DecState& d, const uint32_t* __restrict__ w, int lane) {
+// the thread-per-sub-stream decoder's state ("lanes" below): the next word waits in a register
+struct LaneDec {
+  uint64_t x;
+  int pos, len;    // next word to read, words in the sub-stream
+  uint32_t nextw;  // words[pos] while pos < len: loaded when the word before it was taken
+  int st;
+};
+
+__device__ __forceinline__ uint32_t dec_next_word(LaneDec& d, const uint32_t* __restrict__ w, int) {
+  if (d.pos < 0 || d.pos >= d.len) {
+    d.st = kStOverrun;
+    return 0;
+  }
+  const uint32_t r = d.nextw;
+  ++d.pos;
+  d.nextw = d.pos < d.len ? w[d.pos] : 0u;
+  return r;
+}
+
+// D = DecState or LaneDec in what follows: the arithmetic is one, only dec_next_word differs
+template <class D>
+__device__ __forceinline__ void dec_renorm(D& d, const uint32_t* __restrict__ w, int lane) {
+  if (d.x < kRansLow) d.x = (d.x << 32) | dec_next_word(d, w, lane);
+}
+
+// advance over the symbol [start, next) found for cum = x & 0xFFFF: x = freq * (x >> 16) + cum - start, then renormalise
+template <class D>
+__device__ __forceinline__ void dec_advance(D& d, const uint32_t* __restrict__ w, int lane, int cum, int start,
+                                            int next) {
+  d.x = (uint64_t)(uint32_t)(next - start) * (d.x >> 16) + (uint64_t)(uint32_t)cum - (uint32_t)start;
+  dec_renorm(d, w, lane);
+}
+
+template <class D>
+__device__ __forceinline__ uint32_t dec_get_bits4(D& d, const uint32_t* __restrict__ w, int lane) {
   const uint32_t v = (uint32_t)(d.x & 15u);
   d.x >>= 4;
-  if (d.x < kRansLow) d.x = (d.x << 32) | dec_next_word(d, w, lane);
+  dec_renorm(d, w, lane);
   return v;
+}
+
+// the escape read: the count digit, then the raw value LSB digit first -> the value (kStEscape: more than 8 digits)
+template <class D>
+__device__ __forceinline__ int dec_escape(D& d, const uint32_t* __restrict__ w, int lane, int max_value) {
+  int value = max_value;
+  const uint32_t ndig = dec_get_bits4(d, w, lane);  // 15 = "another count digit follows": more than 8 anyway
+  if (ndig > 8) {
+    d.st = kStEscape;
+  } else {
+    uint32_t raw = 0;
+    for (uint32_t q = 0; q < 8; ++q)
+      if (q < ndig && d.st == 0) raw |= dec_get_bits4(d, w, lane) << (4 * q);
+    const int half = (int)(raw >> 1);
+    value = (raw & 1) ? -half - 1 : half + max_value;
+  }
+  return value;
+}
+
+// open a (sub-)stream of d.len words at word `off`: the state flush on the first call, the carried state and cursor
+// after it -> the stream's words (read only while d.st == 0)
+template <class D>
+__device__ __forceinline__ const uint32_t* dec_open(D& d, const uint32_t* __restrict__ words, long long total_words,
+                                                    long long off, int first, unsigned long long state, int pos) {
+  if (d.st == 0 && (off < 0 || d.len < 2 || off + d.len > total_words)) d.st = kStStream;
+  const uint32_t* __restrict__ w = words + (d.st == 0 ? off : 0);
+  if (d.st == 0) {
+    if (first) {
+      d.x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+      d.pos = 2;
+    } else {
+      d.x = state;
+      d.pos = pos;
+      if (d.pos < 2 || d.pos > d.len) d.st = kStStream;
+    }
+  }
+  return w;
+}
+
+// s_win[r][i] = entry win_start(size) + i of row r < win_rows, INT_MAX past its end; one 64-thread block
+__device__ __forceinline__ void dec_fill_windows(int* __restrict__ s_win, int win_rows, const int* __restrict__ cdfs,
+                                                 int cdf_stride, const int* __restrict__ sizes, int t) {
+#pragma unroll 4
+  for (int r = 0; r < win_rows; ++r) {
+    const int size = sizes[r], ent = win_start(size) + t;
+    s_win[r * kWave + t] = ent < size ? cdfs[(size_t)r * cdf_stride + ent] : INT_MAX;
+  }
+  __syncthreads();
 }
 
 __global__ void __launch_bounds__(kWave)
@@ -276,28 +390,10 @@ rans_decode_streams_kernel(const uint32_t* __restrict__ words, long long total_w
                            int* __restrict__ pos, int* __restrict__ status, int first) {
   extern __shared__ int s_win[];  // [win_rows][64]: entries win_start(size) + l of each row, INT_MAX past its end
   const int b = blockIdx.x, lane = threadIdx.x;
-#pragma unroll 4
-  for (int r = 0; r < win_rows; ++r) {
-    const int size = sizes[r], ent = win_start(size) + lane;
-    s_win[r * kWave + lane] = ent < size ? cdfs[(size_t)r * cdf_stride + ent] : INT_MAX;
-  }
-  __syncthreads();
+  dec_fill_windows(s_win, win_rows, cdfs, cdf_stride, sizes, lane);
 
-  DecState d{0, 0, 0, 0, 0u, first ? 0 : status[b]};
-  const long long off = woff[b];
-  d.len = wlen[b];
-  if (d.st == 0 && (off < 0 || d.len < 2 || off + d.len > total_words)) d.st = kStStream;
-  const uint32_t* __restrict__ w = words + (d.st == 0 ? off : 0);  // read only while st == 0
-  if (d.st == 0) {
-    if (first) {
-      d.x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-      d.pos = 2;
-    } else {
-      d.x = state[b];
-      d.pos = pos[b];
-      if (d.pos < 2 || d.pos > d.len) d.st = kStStream;
-    }
-  }
+  DecState d{0, 0, wlen[b], 0, 0u, first ? 0 : status[b]};
+  const uint32_t* __restrict__ w = dec_open(d, words, total_words, woff[b], first, state[b], pos[b]);
   if (d.st == 0) {
     d.wbase = d.pos;
     d.wbuf = d.pos + lane < d.len ? w[d.pos + lane] : 0u;
@@ -380,23 +476,9 @@ rans_decode_streams_kernel(const uint32_t* __restrict__ words, long long total_w
         d.st = kStSymbol;
         break;
       }
-      // advance: x = freq * (x >> 16) + (x & 0xFFFF) - start, then renormalise
-      d.x = (uint64_t)(uint32_t)(next - start) * (d.x >> 16) + (uint64_t)(uint32_t)cum - (uint32_t)start;
-      if (d.x < kRansLow) d.x = (d.x << 32) | dec_next_word(d, w, lane);
+      dec_advance(d, w, lane, cum, start, next);
       int value = s;
-      const int max_value = size - 2;
-      if (s == max_value && d.st == 0) {
-        const uint32_t ndig = dec_get_bits4(d, w, lane);  // 15 = "another count digit follows": more than 8 anyway
-        if (ndig > 8) {
-          d.st = kStEscape;
-          break;
-        }
-        uint32_t raw = 0;
-        for (uint32_t q = 0; q < 8; ++q)
-          if (q < ndig && d.st == 0) raw |= dec_get_bits4(d, w, lane) << (4 * q);
-        const int half = (int)(raw >> 1);
-        value = (raw & 1) ? -half - 1 : half + max_value;
-      }
+      if (s == size - 2 && d.st == 0) value = dec_escape(d, w, lane, size - 2);
       if (d.st) break;
       if (lane == k) myval = (int)((uint32_t)value + (uint32_t)off_l);
     }
@@ -421,29 +503,6 @@ rans_decode_streams_kernel(const uint32_t* __restrict__ words, long long total_w
 // segment (coalesced).  State, slab tail / word cursor and escape handling are per-thread registers in plain
 // divergent code; the loads are software-pipelined over the steps exactly as the kernels above pipeline chunks.
 // A stream's status is the maximum over its lanes (a shuffle reduction, then one store by lane 0).
-struct LaneEnc {
-  uint64_t x;
-  int head;  // words [head, cap) of the slab are written
-  int st;
-};
-
-__device__ __forceinline__ void lane_emit(LaneEnc& e, uint32_t* __restrict__ slab) {
-  if (e.head <= 0) {  // the slab is full: stop this sub-stream, never write outside it
-    e.st = kStOverflow;
-    return;
-  }
-  --e.head;
-  slab[e.head] = (uint32_t)e.x;
-  e.x >>= 32;
-}
-
-__device__ __forceinline__ void lane_put_bits(LaneEnc& e, uint32_t* __restrict__ slab, uint32_t val) {
-  if (e.st) return;
-  if (e.x >= (1ull << 59)) lane_emit(e, slab);
-  if (e.st) return;
-  e.x = (e.x << 4) | val;
-}
-
 __device__ __forceinline__ int group_max(int v, int L) {
   for (int m = 1; m < L; m <<= 1) v = max(v, __shfl_xor(v, m, kWave));
   return v;
@@ -462,7 +521,7 @@ rans_encode_lanes_kernel(const int* __restrict__ sym, long long sym_ss, long lon
   uint32_t* __restrict__ slab = slabs + (size_t)q * cap;
   const int* __restrict__ symb = sym + (active ? b * sym_ts : 0);
   const int* __restrict__ idxb = idx + (active ? b * idx_ts : 0);
-  LaneEnc e{kRansLow, (int)cap, 0};
+  EncState e{kRansLow, cap, 0};
   const int nsteps = (seg_len + L - 1) >> lg;  // steps per segment; lane l has a symbol in step s if s * L + l < seg_len
   const int T = nseg * nsteps;
   // pipeline registers, one step per stage, steps in reverse (last segment, last step first).  Stage A: index and
@@ -475,39 +534,19 @@ rans_encode_lanes_kernel(const int* __restrict__ sym, long long sym_ss, long lon
   uint32_t c_start = 0, c_next = 1, c_raw = 0, c_flags = 0;  // flags: escaped | ndig << 1 | bad index << 8 | valid << 9
   for (int it = 0; it < T + 3; ++it) {
     // ---- D: fields of the symbol put in this iteration, from the cdf entries loaded one iteration ago
-    const uint32_t freq = c_next - c_start;
-    uint32_t shift = 0;
-    uint64_t rcp = ~0ull;
-    uint32_t d_bias = c_start + (1u << 16) - 1;  // freq 1: q = x - 1, so x + bias + q (2^16 - 1) = (x << 16) + start
-    if (freq >= 2) {
-      rcp = enc_reciprocal(freq, shift);
-      d_bias = c_start;
-    }
+    const EncSymbol d = enc_symbol(c_start, c_next);
     const uint32_t d_raw = c_raw, d_flags = c_flags;
     // ---- C: clamp and escape the value, issue the loads of cdf[value] and cdf[value + 1]
     c_flags = 0;
     c_start = 0;
     c_next = 1;
     if (b_ok) {
-      const int max_value = b_size - 2;
-      int value = (int)((uint32_t)b_v - (uint32_t)b_off);
-      uint32_t raw = 0, esc = 0, ndig = 0;
-      if (value < 0) {
-        raw = (uint32_t)(-2 * (long long)value - 1);
-        value = max_value;
-      } else if (value >= max_value) {
-        raw = (uint32_t)(2 * (long long)(value - max_value));
-        value = max_value;
-      }
-      if (value == max_value) {
-        esc = 1;
-        ndig = raw ? 8u - ((uint32_t)__clz((int)raw) >> 2) : 0u;  // nibbles up to the top non-zero one
-      }
+      const EncValue v = enc_clamp_escape(b_v, b_off, b_size);
       const int* __restrict__ row = cdfs + (size_t)b_ci * cdf_stride;
-      c_start = (uint32_t)row[value];
-      c_next = (uint32_t)row[value + 1];
-      c_raw = raw;
-      c_flags = esc | (ndig << 1) | (b_bad ? 1u << 8 : 0u) | (1u << 9);
+      c_start = (uint32_t)row[v.value];
+      c_next = (uint32_t)row[v.value + 1];
+      c_raw = v.raw;
+      c_flags = v.esc | (v.ndig << 1) | (b_bad ? 1u << 8 : 0u) | (1u << 9);
     }
     // ---- B: the row's size and offset (a bad index reads row 0 and is never put)
     b_ok = a_ok;
@@ -540,58 +579,23 @@ rans_encode_lanes_kernel(const int* __restrict__ sym, long long sym_ss, long lon
     }
     if (d_flags & 1u) {
       const int ndig = (int)((d_flags >> 1) & 15u);
-      for (int d = 7; d >= 0; --d)
-        if (d < ndig) lane_put_bits(e, slab, (d_raw >> (4 * d)) & 15u);
-      lane_put_bits(e, slab, (uint32_t)ndig);
+      for (int g = 7; g >= 0; --g)
+        if (g < ndig) enc_put_bits(e, slab, true, (d_raw >> (4 * g)) & 15u);
+      enc_put_bits(e, slab, true, (uint32_t)ndig);
       if (e.st) continue;
     }
-    if ((uint32_t)(e.x >> 32) >= (freq << 15)) {  // x >= freq << 47
-      lane_emit(e, slab);
+    if (enc_must_emit(e.x, d.freq)) {
+      enc_emit(e, slab, true);
       if (e.st) continue;
     }
-    const uint64_t qd = __umul64hi(e.x, rcp) >> shift;
-    e.x = e.x + d_bias + qd * (uint64_t)((1u << 16) - freq);
+    e.x = enc_put(e.x, d.freq, d.shift, d.rcp, d.bias);
   }
-  // 8-byte state flush, low word first in the stream
-  if (active && e.st == 0) {
-    if (e.head < 2) {
-      e.st = kStOverflow;
-    } else {
-      e.head -= 2;
-      slab[e.head + 1] = (uint32_t)(e.x >> 32);
-      slab[e.head] = (uint32_t)e.x;
-    }
-  }
+  if (active) enc_flush(e, slab, true);
   const int st = group_max(active ? e.st : 0, L);
   if (active) {
-    nwords[q] = st ? 0 : (int)cap - e.head;
+    nwords[q] = st ? 0 : (int)(cap - e.head);
     if (l == 0) status[b] = st;
   }
-}
-
-struct LaneDec {
-  uint64_t x;
-  int pos, len;    // next word to read, words in the sub-stream
-  uint32_t nextw;  // words[pos] while pos < len: loaded when the word before it was taken
-  int st;
-};
-
-__device__ __forceinline__ uint32_t lane_next_word(LaneDec& d, const uint32_t* __restrict__ w) {
-  if (d.pos < 0 || d.pos >= d.len) {
-    d.st = kStOverrun;
-    return 0;
-  }
-  const uint32_t r = d.nextw;
-  ++d.pos;
-  d.nextw = d.pos < d.len ? w[d.pos] : 0u;
-  return r;
-}
-
-__device__ __forceinline__ uint32_t lane_get_bits4(LaneDec& d, const uint32_t* __restrict__ w) {
-  const uint32_t v = (uint32_t)(d.x & 15u);
-  d.x >>= 4;
-  if (d.x < kRansLow) d.x = (d.x << 32) | lane_next_word(d, w);
-  return v;
 }
 
 __global__ void __launch_bounds__(kWave)
@@ -603,34 +607,17 @@ rans_decode_lanes_kernel(const uint32_t* __restrict__ words, long long total_wor
                          int* __restrict__ pos, int* __restrict__ status, int first, int lg) {
   extern __shared__ int s_win[];  // [win_rows][64]: entries win_start(size) + i of each row, INT_MAX past its end
   const int L = 1 << lg, t = threadIdx.x;
-#pragma unroll 4
-  for (int r = 0; r < win_rows; ++r) {
-    const int size = sizes[r], ent = win_start(size) + t;
-    s_win[r * kWave + t] = ent < size ? cdfs[(size_t)r * cdf_stride + ent] : INT_MAX;
-  }
-  __syncthreads();
+  dec_fill_windows(s_win, win_rows, cdfs, cdf_stride, sizes, t);
 
   const int b = blockIdx.x * (kWave >> lg) + (t >> lg), l = t & (L - 1);
   const bool active = b < nstreams;
   const long long q = active ? (long long)b * L + l : 0;
   LaneDec d{0, 0, 0, 0u, 0};
-  long long off = 0;
+  const uint32_t* __restrict__ w = words;
   if (active) {
     d.st = first ? 0 : status[b];
-    off = woff[q];
     d.len = wlen[q];
-    if (d.st == 0 && (off < 0 || d.len < 2 || off + d.len > total_words)) d.st = kStStream;
-  }
-  const uint32_t* __restrict__ w = words + (active && d.st == 0 ? off : 0);  // read only while st == 0
-  if (active && d.st == 0) {
-    if (first) {
-      d.x = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-      d.pos = 2;
-    } else {
-      d.x = state[q];
-      d.pos = pos[q];
-      if (d.pos < 2 || d.pos > d.len) d.st = kStStream;
-    }
+    w = dec_open(d, words, total_words, woff[q], first, state[q], pos[q]);
     if (d.st == 0) d.nextw = d.pos < d.len ? w[d.pos] : 0u;
   }
   const int* __restrict__ idxb = idx + (active ? b * idx_ts : 0);
@@ -716,23 +703,9 @@ rans_decode_lanes_kernel(const uint32_t* __restrict__ words, long long total_wor
       if (s < 0 || s > size - 2) {
         d.st = kStSymbol;
       } else {
-        // advance: x = freq * (x >> 16) + (x & 0xFFFF) - start, then renormalise
-        d.x = (uint64_t)(uint32_t)(next - start) * (d.x >> 16) + (uint64_t)(uint32_t)cum - (uint32_t)start;
-        if (d.x < kRansLow) d.x = (d.x << 32) | lane_next_word(d, w);
+        dec_advance(d, w, t, cum, start, next);
         int value = s;
-        const int max_value = size - 2;
-        if (s == max_value && d.st == 0) {
-          const uint32_t ndig = lane_get_bits4(d, w);  // 15 = "another count digit follows": more than 8 anyway
-          if (ndig > 8) {
-            d.st = kStEscape;
-          } else {
-            uint32_t raw = 0;
-            for (uint32_t g = 0; g < 8; ++g)
-              if (g < ndig && d.st == 0) raw |= lane_get_bits4(d, w) << (4 * g);
-            const int half = (int)(raw >> 1);
-            value = (raw & 1) ? -half - 1 : half + max_value;
-          }
-        }
+        if (s == size - 2 && d.st == 0) value = dec_escape(d, w, t, size - 2);
         if (d.st == 0) outv = (int)((uint32_t)value + (uint32_t)off_l);
       }
     }
@@ -757,30 +730,104 @@ extern "C" long long tmae_rans_stream_cap_words(long long nsymbols) {
   return (52 * nsymbols + 31) / 32 + (nsymbols >> 19) + 3;
 }
 
-#define RANSD_TABLES(name)                                                                             \
-  TMAE_REQUIRE(cdfs && cdf_sizes && offsets && ncdf > 0 && cdf_stride > 1, name ": CDF tables required")
+// log2 of a lane count that is a power of two in 1..64, -1 otherwise
+static int lanes_log2(int lanes) {
+  for (int lg = 0; lg <= 6; ++lg)
+    if (lanes == 1 << lg) return lg;
+  return -1;
+}
 
-#define RANSD_SHAPE(name)                                                                                          \
-  TMAE_REQUIRE(nstreams > 0, name ": nstreams = %d must be positive", nstreams);                                   \
-  TMAE_REQUIRE(nseg > 0 && seg_len > 0 && (long long)nseg * seg_len <= (1ll << 30),                                \
-               name ": nseg * seg_len = %d * %d must be in [1, 2^30]", nseg, seg_len)
+// what the encode and the decode entry points require alike; `name` is the entry point, for the message
+static int check_common(const char* name, bool buffers, int nstreams, int nseg, int seg_len, const void* cdfs,
+                        int cdf_stride, const void* cdf_sizes, const void* offsets, int ncdf, int lanes, int* lg) {
+  TMAE_REQUIRE(buffers, "%s: NULL buffer", name);
+  TMAE_REQUIRE(nstreams > 0, "%s: nstreams = %d must be positive", name, nstreams);
+  TMAE_REQUIRE(nseg > 0 && seg_len > 0 && (long long)nseg * seg_len <= (1ll << 30),
+               "%s: nseg * seg_len = %d * %d must be in [1, 2^30]", name, nseg, seg_len);
+  TMAE_REQUIRE(cdfs && cdf_sizes && offsets && ncdf > 0 && cdf_stride > 1, "%s: CDF tables required", name);
+  *lg = lanes_log2(lanes);
+  TMAE_REQUIRE(*lg >= 0, "%s: lanes = %d must be a power of two in 1..64", name, lanes);
+  TMAE_REQUIRE((long long)nstreams * lanes <= INT32_MAX, "%s: nstreams * lanes = %d * %d overflows int32", name,
+               nstreams, lanes);
+  return TMAE_OK;
+}
+
+// lanes = 1 with the wave-per-stream kernel (by_wave) is tmae_rans_encode_streams, else tmae_rans_encode_lanes
+static int encode_entry(const char* name, bool by_wave, const int32_t* symbols, long long sym_seg_stride,
+                        long long sym_stream_stride, const int32_t* indexes, long long idx_seg_stride,
+                        long long idx_stream_stride, int nstreams, int nseg, int seg_len, const int32_t* cdfs,
+                        int cdf_stride, const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
+                        long long cap_words, int32_t* nwords, int32_t* status, int lanes, void* stream) {
+  int lg = 0;
+  if (int rc = check_common(name, symbols && indexes && slabs && nwords && status, nstreams, nseg, seg_len, cdfs,
+                            cdf_stride, cdf_sizes, offsets, ncdf, lanes, &lg))
+    return rc;
+  TMAE_REQUIRE(cap_words > 0 && cap_words <= INT32_MAX, "%s: cap_words = %lld outside [1, 2^31)", name, cap_words);
+  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
+               "%s: negative stride", name);
+  if (by_wave) {
+    hipLaunchKernelGGL(rans_encode_streams_kernel, dim3(nstreams), dim3(kWave), 0, (hipStream_t)stream, symbols,
+                       sym_seg_stride, sym_stream_stride, indexes, idx_seg_stride, idx_stream_stride, nseg, seg_len,
+                       cdfs, cdf_stride, cdf_sizes, offsets, ncdf, slabs, cap_words, nwords, status);
+  } else {
+    const int per_wave = kWave >> lg;
+    hipLaunchKernelGGL(rans_encode_lanes_kernel, dim3((nstreams + per_wave - 1) / per_wave), dim3(kWave), 0,
+                       (hipStream_t)stream, symbols, sym_seg_stride, sym_stream_stride, indexes, idx_seg_stride,
+                       idx_stream_stride, nstreams, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf, slabs,
+                       cap_words, nwords, status, lg);
+  }
+  TMAE_LAUNCH_CHECK(name);
+}
+
+static int decode_entry(const char* name, bool by_wave, const uint32_t* words, long long total_words,
+                        const long long* word_offsets, const int32_t* word_counts, const int32_t* indexes,
+                        long long idx_seg_stride, long long idx_stream_stride, int32_t* symbols,
+                        long long sym_seg_stride, long long sym_stream_stride, int nstreams, int seg0, int nseg,
+                        int seg_len, const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
+                        const int32_t* offsets, int ncdf, unsigned long long* state, int32_t* pos, int32_t* status,
+                        int first, int lanes, void* stream) {
+  int lg = 0;
+  if (int rc = check_common(name, words && word_offsets && word_counts && indexes && symbols && state && pos && status,
+                            nstreams, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf, lanes, &lg))
+    return rc;
+  TMAE_REQUIRE(total_words > 0 && seg0 >= 0, "%s: total_words = %lld, seg0 = %d", name, total_words, seg0);
+  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
+               "%s: negative stride", name);
+  const int win_rows = ncdf < kMaxWinRows ? ncdf : kMaxWinRows;
+  const size_t lds = (size_t)win_rows * kWave * sizeof(int);
+  if (by_wave) {
+    hipLaunchKernelGGL(rans_decode_streams_kernel, dim3(nstreams), dim3(kWave), lds, (hipStream_t)stream, words,
+                       total_words, word_offsets, word_counts, indexes, idx_seg_stride, idx_stream_stride, symbols,
+                       sym_seg_stride, sym_stream_stride, seg0, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets,
+                       ncdf, win_rows, state, pos, status, first ? 1 : 0);
+  } else {
+    const int per_wave = kWave >> lg;
+    hipLaunchKernelGGL(rans_decode_lanes_kernel, dim3((nstreams + per_wave - 1) / per_wave), dim3(kWave), lds,
+                       (hipStream_t)stream, words, total_words, word_offsets, word_counts, indexes, idx_seg_stride,
+                       idx_stream_stride, symbols, sym_seg_stride, sym_stream_stride, nstreams, seg0, nseg, seg_len,
+                       cdfs, cdf_stride, cdf_sizes, offsets, ncdf, win_rows, state, pos, status, first ? 1 : 0, lg);
+  }
+  TMAE_LAUNCH_CHECK(name);
+}
 
 extern "C" int tmae_rans_encode_streams(const int32_t* symbols, long long sym_seg_stride, long long sym_stream_stride,
                                         const int32_t* indexes, long long idx_seg_stride, long long idx_stream_stride,
                                         int nstreams, int nseg, int seg_len, const int32_t* cdfs, int cdf_stride,
                                         const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
                                         long long cap_words, int32_t* nwords, int32_t* status, void* stream) {
-  TMAE_REQUIRE(symbols && indexes && slabs && nwords && status, "tmae_rans_encode_streams: NULL buffer");
-  RANSD_SHAPE("tmae_rans_encode_streams");
-  RANSD_TABLES("tmae_rans_encode_streams");
-  TMAE_REQUIRE(cap_words > 0 && cap_words <= INT32_MAX, "tmae_rans_encode_streams: cap_words = %lld outside [1, 2^31)",
-               cap_words);
-  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
-               "tmae_rans_encode_streams: negative stride");
-  hipLaunchKernelGGL(rans_encode_streams_kernel, dim3(nstreams), dim3(kWave), 0, (hipStream_t)stream, symbols,
-                     sym_seg_stride, sym_stream_stride, indexes, idx_seg_stride, idx_stream_stride, nseg, seg_len, cdfs,
-                     cdf_stride, cdf_sizes, offsets, ncdf, slabs, cap_words, nwords, status);
-  TMAE_LAUNCH_CHECK("tmae_rans_encode_streams");
+  return encode_entry("tmae_rans_encode_streams", true, symbols, sym_seg_stride, sym_stream_stride, indexes,
+                      idx_seg_stride, idx_stream_stride, nstreams, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets,
+                      ncdf, slabs, cap_words, nwords, status, 1, stream);
+}
+
+extern "C" int tmae_rans_encode_lanes(const int32_t* symbols, long long sym_seg_stride, long long sym_stream_stride,
+                                      const int32_t* indexes, long long idx_seg_stride, long long idx_stream_stride,
+                                      int nstreams, int nseg, int seg_len, const int32_t* cdfs, int cdf_stride,
+                                      const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
+                                      long long cap_words, int32_t* nwords, int32_t* status, int lanes, void* stream) {
+  return encode_entry("tmae_rans_encode_lanes", false, symbols, sym_seg_stride, sym_stream_stride, indexes,
+                      idx_seg_stride, idx_stream_stride, nstreams, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets,
+                      ncdf, slabs, cap_words, nwords, status, lanes, stream);
 }
 
 extern "C" int tmae_rans_pack_streams(const uint32_t* slabs, long long cap_words, const int32_t* nwords, int nstreams,
@@ -801,54 +848,9 @@ extern "C" int tmae_rans_decode_streams(const uint32_t* words, long long total_w
                                         const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
                                         const int32_t* offsets, int ncdf, unsigned long long* state, int32_t* pos,
                                         int32_t* status, int first, void* stream) {
-  TMAE_REQUIRE(words && word_offsets && word_counts && indexes && symbols && state && pos && status,
-               "tmae_rans_decode_streams: NULL buffer");
-  RANSD_SHAPE("tmae_rans_decode_streams");
-  RANSD_TABLES("tmae_rans_decode_streams");
-  TMAE_REQUIRE(total_words > 0 && seg0 >= 0, "tmae_rans_decode_streams: total_words = %lld, seg0 = %d", total_words,
-               seg0);
-  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
-               "tmae_rans_decode_streams: negative stride");
-  const int win_rows = ncdf < kMaxWinRows ? ncdf : kMaxWinRows;
-  hipLaunchKernelGGL(rans_decode_streams_kernel, dim3(nstreams), dim3(kWave), (size_t)win_rows * kWave * sizeof(int),
-                     (hipStream_t)stream, words, total_words, word_offsets, word_counts, indexes, idx_seg_stride,
-                     idx_stream_stride, symbols, sym_seg_stride, sym_stream_stride, seg0, nseg, seg_len, cdfs,
-                     cdf_stride, cdf_sizes, offsets, ncdf, win_rows, state, pos, status, first ? 1 : 0);
-  TMAE_LAUNCH_CHECK("tmae_rans_decode_streams");
-}
-
-// log2 of a lane count that is a power of two in 1..64, -1 otherwise
-static int lanes_log2(int lanes) {
-  for (int lg = 0; lg <= 6; ++lg)
-    if (lanes == 1 << lg) return lg;
-  return -1;
-}
-
-#define RANSD_LANES(name)                                                                                     \
-  const int lg = lanes_log2(lanes);                                                                           \
-  TMAE_REQUIRE(lg >= 0, name ": lanes = %d must be a power of two in 1..64", lanes);                          \
-  TMAE_REQUIRE((long long)nstreams * lanes <= INT32_MAX, name ": nstreams * lanes = %d * %d overflows int32", \
-               nstreams, lanes)
-
-extern "C" int tmae_rans_encode_lanes(const int32_t* symbols, long long sym_seg_stride, long long sym_stream_stride,
-                                      const int32_t* indexes, long long idx_seg_stride, long long idx_stream_stride,
-                                      int nstreams, int nseg, int seg_len, const int32_t* cdfs, int cdf_stride,
-                                      const int32_t* cdf_sizes, const int32_t* offsets, int ncdf, uint32_t* slabs,
-                                      long long cap_words, int32_t* nwords, int32_t* status, int lanes, void* stream) {
-  TMAE_REQUIRE(symbols && indexes && slabs && nwords && status, "tmae_rans_encode_lanes: NULL buffer");
-  RANSD_SHAPE("tmae_rans_encode_lanes");
-  RANSD_TABLES("tmae_rans_encode_lanes");
-  RANSD_LANES("tmae_rans_encode_lanes");
-  TMAE_REQUIRE(cap_words > 0 && cap_words <= INT32_MAX, "tmae_rans_encode_lanes: cap_words = %lld outside [1, 2^31)",
-               cap_words);
-  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
-               "tmae_rans_encode_lanes: negative stride");
-  const int per_wave = kWave >> lg;
-  hipLaunchKernelGGL(rans_encode_lanes_kernel, dim3((nstreams + per_wave - 1) / per_wave), dim3(kWave), 0,
-                     (hipStream_t)stream, symbols, sym_seg_stride, sym_stream_stride, indexes, idx_seg_stride,
-                     idx_stream_stride, nstreams, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf, slabs,
-                     cap_words, nwords, status, lg);
-  TMAE_LAUNCH_CHECK("tmae_rans_encode_lanes");
+  return decode_entry("tmae_rans_decode_streams", true, words, total_words, word_offsets, word_counts, indexes,
+                      idx_seg_stride, idx_stream_stride, symbols, sym_seg_stride, sym_stream_stride, nstreams, seg0, nseg,
+                      seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf, state, pos, status, first, 1, stream);
 }
 
 extern "C" int tmae_rans_decode_lanes(const uint32_t* words, long long total_words, const long long* word_offsets,
@@ -858,21 +860,7 @@ extern "C" int tmae_rans_decode_lanes(const uint32_t* words, long long total_wor
                                       const int32_t* cdfs, int cdf_stride, const int32_t* cdf_sizes,
                                       const int32_t* offsets, int ncdf, unsigned long long* state, int32_t* pos,
                                       int32_t* status, int first, int lanes, void* stream) {
-  TMAE_REQUIRE(words && word_offsets && word_counts && indexes && symbols && state && pos && status,
-               "tmae_rans_decode_lanes: NULL buffer");
-  RANSD_SHAPE("tmae_rans_decode_lanes");
-  RANSD_TABLES("tmae_rans_decode_lanes");
-  RANSD_LANES("tmae_rans_decode_lanes");
-  TMAE_REQUIRE(total_words > 0 && seg0 >= 0, "tmae_rans_decode_lanes: total_words = %lld, seg0 = %d", total_words,
-               seg0);
-  TMAE_REQUIRE(sym_seg_stride >= 0 && sym_stream_stride >= 0 && idx_seg_stride >= 0 && idx_stream_stride >= 0,
-               "tmae_rans_decode_lanes: negative stride");
-  const int win_rows = ncdf < kMaxWinRows ? ncdf : kMaxWinRows;
-  const int per_wave = kWave >> lg;
-  hipLaunchKernelGGL(rans_decode_lanes_kernel, dim3((nstreams + per_wave - 1) / per_wave), dim3(kWave),
-                     (size_t)win_rows * kWave * sizeof(int), (hipStream_t)stream, words, total_words, word_offsets,
-                     word_counts, indexes, idx_seg_stride, idx_stream_stride, symbols, sym_seg_stride,
-                     sym_stream_stride, nstreams, seg0, nseg, seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf,
-                     win_rows, state, pos, status, first ? 1 : 0, lg);
-  TMAE_LAUNCH_CHECK("tmae_rans_decode_lanes");
+  return decode_entry("tmae_rans_decode_lanes", false, words, total_words, word_offsets, word_counts, indexes,
+                      idx_seg_stride, idx_stream_stride, symbols, sym_seg_stride, sym_stream_stride, nstreams, seg0, nseg,
+                      seg_len, cdfs, cdf_stride, cdf_sizes, offsets, ncdf, state, pos, status, first, lanes, stream);
 }

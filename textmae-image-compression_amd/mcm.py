@@ -687,18 +687,9 @@ class _Executor:
         the host rANS coder: one z string per image, ONE y string for the whole batch (slice-major)."""
         from .coder import BufferedRansEncoder
 
-        m, B = self.m, self.batch
-        N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
-        eb, gc = m.entropy_bottleneck, m.gaussian_conditional
-        imgs = self._check_imgs(imgs)
-        shuf, rest = self._front(imgs, scores)
-        # z: symbols round(z - median); z_hat = symbols + median (= EB.decompress of its own strings)
-        ops.eb_likelihood(eb, self.Z, B, N, hz * hz, lik=self.ZLIK, zhat=self.ZHAT, table=self.eb_table)
-        zsym = ops.eb_symbols(eb, self.Z, B, N, hz * hz, table=self.eb_table)
-        self._h_s()
-        sym = torch.empty(S * B * sw * HW, dtype=torch.int32, device=self.device)
-        idx = torch.empty_like(sym)
-        self._slices(self._gc_compress(sym, idx))
+        B, hz = self.batch, self.hz
+        eb, gc = self.m.entropy_bottleneck, self.m.gaussian_conditional
+        zsym, sym, idx, rest = self._analysis(imgs, scores)
         zsym_h, sym_h, idx_h = zsym.cpu().numpy(), sym.cpu().numpy(), idx.cpu().numpy()
         self.last_streams = {"z_symbols": zsym_h, "y_symbols": sym_h, "y_indexes": idx_h}  # rate diagnostics
         zidx = eb._channel_indexes(hz * hz)
@@ -727,41 +718,43 @@ class _Executor:
         shuf = ops.invert_permutation(ids_restore.to(self.device))
         return self._back(shuf, m.encoder_embed.proj.in_channels)
 
-    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1):
-        """compress with the device coder: the same symbol / index buffers, coded as one y and one z stream per
-        image (image b's y stream = its [slice][channel][pixel] symbols), the reference's batch-1 format B times;
-        with lanes / z_lanes > 1 a stream becomes a lane-interleaved record (coder.encode_record)"""
-        from .coder import DeviceRansEncoder
-
+    def _analysis(self, imgs, scores):
+        """the eval forward's analysis path with symbol / index outputs -> (zsym [B][N][hz*hz], y sym and idx
+        [slice][image][channel][pixel], ids_restore), all on the device"""
         m, B = self.m, self.batch
         N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
-        eb, gc = m.entropy_bottleneck, m.gaussian_conditional
-        imgs = self._check_imgs(imgs)
-        shuf, rest = self._front(imgs, scores)
+        eb = m.entropy_bottleneck
+        shuf, rest = self._front(self._check_imgs(imgs), scores)
+        # z: symbols round(z - median); z_hat = symbols + median (= EB.decompress of its own strings)
         ops.eb_likelihood(eb, self.Z, B, N, hz * hz, lik=self.ZLIK, zhat=self.ZHAT, table=self.eb_table)
         zsym = ops.eb_symbols(eb, self.Z, B, N, hz * hz, table=self.eb_table)
         self._h_s()
         sym = torch.empty(S * B * sw * HW, dtype=torch.int32, device=self.device)
         idx = torch.empty_like(sym)
         self._slices(self._gc_compress(sym, idx))
+        return zsym, sym, idx, rest
+
+    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1):
+        """compress with the device coder: the same symbol / index buffers, coded as one y and one z record per
+        image (image b's y stream = its [slice][channel][pixel] symbols) of lanes / z_lanes lanes
+        (coder.encode_record); one lane is the plain stream, the reference's batch-1 format B times"""
+        from .coder import DeviceRansEncoder
+
+        m, B = self.m, self.batch
+        N, S, hz, per = m.hyperprior_depth, m.num_slices, self.hz, self.sw * self.g * self.g
+        eb, gc = m.entropy_bottleneck, m.gaussian_conditional
+        zsym, sym, idx, rest = self._analysis(imgs, scores)
         enc = self.__dict__.get("_dev_encoder")
         if enc is None:
             enc = self._dev_encoder = DeviceRansEncoder()
-        zidx = self._z_indexes()
         nz = N * hz * hz
-        if (lanes, z_lanes) == (1, 1):
-            z_strings = enc.encode_streams(zsym, (0, nz), zidx, (0, 0), B, 1, nz, eb.device_tables(),
-                                           what="z stream of image")
-            y_strings = enc.encode_streams(sym, (B * sw * HW, sw * HW), idx, (B * sw * HW, sw * HW), B, S, sw * HW,
-                                           gc.device_tables(), what="y stream of image")
-        else:
-            z_strings = enc.encode_records(zsym, (0, nz), zidx, (0, 0), B, 1, nz, eb.device_tables(), z_lanes,
-                                           what="z stream of image")
-            y_strings = enc.encode_records(sym, (B * sw * HW, sw * HW), idx, (B * sw * HW, sw * HW), B, S, sw * HW,
-                                           gc.device_tables(), lanes, what="y stream of image")
+        z_strings = enc.encode_records(zsym, (0, nz), self._z_indexes(), (0, 0), B, 1, nz, eb.device_tables(), z_lanes,
+                                       what="z stream of image")
+        y_strings = enc.encode_records(sym, (B * per, per), idx, (B * per, per), B, S, per, gc.device_tables(), lanes,
+                                       what="y stream of image")
         self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # rate diagnostics
         out = {"string": [y_strings, z_strings], "shape": torch.Size([hz, hz]), "ids_restore": rest}
-        if (lanes, z_lanes) != (1, 1):
+        if lanes > 1 or z_lanes > 1:
             out["lanes"] = (lanes, z_lanes)
         return out
 
@@ -777,7 +770,7 @@ class _Executor:
         """decompress of per-image records: every string goes up in one copy, the z and y streams are decoded by
         device kernels (the y streams inside the slice loop, one call per slice step), and nothing synchronises with
         the host until the status words are read after the last kernel of _back has been enqueued"""
-        from .coder import DeviceRansDecoder, _raise_status, parse_record
+        from .coder import DeviceRansDecoder, _raise_status
 
         m, B = self.m, self.batch
         N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
@@ -789,20 +782,10 @@ class _Executor:
         bound = float(gc.scale_bound) if gc.scale_bound is not None else 0.11
         zidx = self._z_indexes()
         rest = ids_restore.to(self.device)
-        dec = DeviceRansDecoder()
-        laned = (lanes, z_lanes) != (1, 1)
-        if laned:  # headers are checked here, on the host, before the first launch
-            for part, L, name in ((strings[0], lanes, "y"), (strings[1], z_lanes, "z")):
-                for b, rec in enumerate(part):
-                    try:
-                        parse_record(rec, L)
-                    except ValueError as e:
-                        raise ValueError(f"{name} stream of image {b}: {e}") from None
-            dec.set_records(list(strings[0]) + list(strings[1]), [lanes] * B + [z_lanes] * B, self.device)
-            decode = dec.decode_records
-        else:
-            dec.set_streams(list(strings[0]) + list(strings[1]), self.device)  # streams [0, B): y, [B, 2B): z
-            decode = dec.decode_streams
+        dec = DeviceRansDecoder()  # records [0, B): y, [B, 2B): z; a bad header raises here, before the first launch
+        dec.set_records(list(strings[0]) + list(strings[1]), [lanes] * B + [z_lanes] * B, self.device,
+                        what=[f"{c} stream of image {b}" for c in "yz" for b in range(B)])
+        decode = dec.decode_records
         nz, per = N * hz * hz, B * sw * HW
         zsym = torch.empty((B, N, hz * hz), dtype=torch.int32, device=self.device)
         decode(B, B, zidx, (0, 0), zsym, (0, nz), 0, 1, nz, etabs)

@@ -556,14 +556,71 @@ def _rans_tables(tables):
     return cdf.data_ptr(), cdf.shape[1], sizes.data_ptr(), offsets.data_ptr(), cdf.shape[0]
 
 
+def _rans_nsub(name, lanes, nstreams):
+    """sub-streams of a call; lanes = None is the wave-per-stream entry point: one sub-stream per stream"""
+    from .coder import check_lanes
+
+    lanes = 1 if lanes is None else check_lanes(lanes, f"{name}: ")
+    if nstreams <= 0:
+        raise ValueError(f"{name}: nstreams = {nstreams} must be positive")
+    return nstreams * lanes
+
+
+def _rans_bufs(name, **bufs):
+    """bufs = {what: (tensor, dtype, least number of elements)}: dtype, size and contiguity of all, then the device"""
+    for what, (t, dtype, numel) in bufs.items():
+        if t.dtype != dtype:
+            raise ValueError(f"{name}: {what} must be {dtype}, got {t.dtype}")
+        if t.numel() < numel:
+            raise ValueError(f"{name}: {what} holds {t.numel()} elements, {numel} needed")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous")
+    for what, (t, _, _) in bufs.items():
+        if not t.is_cuda:
+            raise ValueError(f"{name}: {what} must be a device (HIP) tensor")
+
+
+def _rans_encode(name, lanes, symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs,
+                 cap_words, nwords, status):
+    """both encode wrappers: the checks, then tmae_<name> (which takes lanes last where lanes is not None)"""
+    i32, nsub = torch.int32, _rans_nsub(name, lanes, nstreams)
+    if cap_words <= 0:
+        raise ValueError(f"{name}: cap_words = {cap_words} must be positive")
+    _rans_bufs(name, symbols=(symbols, i32, 1), indexes=(indexes, i32, 1), slabs=(slabs, i32, nsub * cap_words),
+               nwords=(nwords, i32, nsub), status=(status, i32, nstreams))
+    _lib.call("tmae_" + name, _p(symbols), sym_strides[0], sym_strides[1], _p(indexes), idx_strides[0], idx_strides[1],
+              nstreams, nseg, seg_len, *_rans_tables(tables), _p(slabs), cap_words, _p(nwords), _p(status),
+              *(() if lanes is None else (lanes,)), _stream())
+
+
+def _rans_decode(name, lanes, words, total_words, word_offsets, word_counts, indexes, idx_strides, symbols, sym_strides,
+                 nstreams, seg0, nseg, seg_len, tables, state, pos, status, first):
+    i32, i64, nsub = torch.int32, torch.int64, _rans_nsub(name, lanes, nstreams)
+    _rans_bufs(name, words=(words, i32, max(int(total_words), 1)), word_offsets=(word_offsets, i64, nsub),
+               word_counts=(word_counts, i32, nsub), indexes=(indexes, i32, 1), symbols=(symbols, i32, 1),
+               state=(state, i64, nsub), pos=(pos, i32, nsub), status=(status, i32, nstreams))
+    _lib.call("tmae_" + name, _p(words), total_words, _p(word_offsets), _p(word_counts), _p(indexes), idx_strides[0],
+              idx_strides[1], _p(symbols), sym_strides[0], sym_strides[1], nstreams, seg0, nseg, seg_len,
+              *_rans_tables(tables), _p(state), _p(pos), _p(status), int(bool(first)),
+              *(() if lanes is None else (lanes,)), _stream())
+
+
 def rans_encode_streams(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap_words,
                         nwords, status):
-    """code nstreams independent rANS streams on the device (csrc/rans_device.hip).  Stream b's segment j is
-    seg_len int32 at base + j * strides[0] + b * strides[1]; stream b lands in the last nwords[b] words of
+    """code nstreams independent rANS streams on the device (csrc/rans_device.hip), one wave each.  Stream b's
+    segment j is seg_len int32 at base + j * strides[0] + b * strides[1]; stream b lands in the last nwords[b] words of
     slabs[b] (cap_words words each); status[b] != 0 where a slab was too small"""
-    _lib.call("tmae_rans_encode_streams", _p(symbols), sym_strides[0], sym_strides[1], _p(indexes), idx_strides[0],
-              idx_strides[1], nstreams, nseg, seg_len, *_rans_tables(tables), _p(slabs), cap_words, _p(nwords),
-              _p(status), _stream())
+    _rans_encode("rans_encode_streams", None, symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len,
+                 tables, slabs, cap_words, nwords, status)
+
+
+def rans_encode_lanes(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap_words,
+                      nwords, status, lanes):
+    """rans_encode_streams with every stream dealt over `lanes` sub-streams, one thread each (sub-stream l of a stream
+    codes the symbols k = l mod lanes of each segment): sub-stream b * lanes + l lands in the last
+    nwords[b * lanes + l] words of slab b * lanes + l; status is per stream ([nstreams])"""
+    _rans_encode("rans_encode_lanes", lanes, symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables,
+                 slabs, cap_words, nwords, status)
 
 
 def rans_pack_streams(slabs, cap_words, nwords, nstreams, dense, dense_cap_words, word_offsets, status):
@@ -576,74 +633,16 @@ def rans_decode_streams(words, total_words, word_offsets, word_counts, indexes, 
                         nstreams, seg0, nseg, seg_len, tables, state, pos, status, first):
     """decode segments [seg0, seg0 + nseg) of nstreams device-resident streams; state (int64 storage of the
     uint64 coder state) / pos / status carry each stream from one call to the next"""
-    _lib.call("tmae_rans_decode_streams", _p(words), total_words, _p(word_offsets), _p(word_counts), _p(indexes),
-              idx_strides[0], idx_strides[1], _p(symbols), sym_strides[0], sym_strides[1], nstreams, seg0, nseg,
-              seg_len, *_rans_tables(tables), _p(state), _p(pos), _p(status), int(bool(first)), _stream())
-
-
-def _rans_lanes(lanes, nstreams, name):
-    """lanes must be a power of two in 1..64 -> sub-streams of the call"""
-    if isinstance(lanes, bool) or not isinstance(lanes, int) or lanes not in (1, 2, 4, 8, 16, 32, 64):
-        raise ValueError(f"{name}: lanes = {lanes!r} must be a power of two in 1..64")
-    if nstreams <= 0:
-        raise ValueError(f"{name}: nstreams = {nstreams} must be positive")
-    return nstreams * lanes
-
-
-def _rans_buf(t, dtype, numel, name, what):
-    if t.dtype != dtype:
-        raise ValueError(f"{name}: {what} must be {dtype}, got {t.dtype}")
-    if t.numel() < numel:
-        raise ValueError(f"{name}: {what} holds {t.numel()} elements, {numel} needed")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: {what} must be contiguous")
-
-
-def _rans_on_device(name, **tensors):
-    for what, t in tensors.items():
-        if not t.is_cuda:
-            raise ValueError(f"{name}: {what} must be a device (HIP) tensor")
-
-
-def rans_encode_lanes(symbols, sym_strides, indexes, idx_strides, nstreams, nseg, seg_len, tables, slabs, cap_words,
-                      nwords, status, lanes):
-    """rans_encode_streams with every stream dealt over `lanes` sub-streams (sub-stream l of a stream codes the
-    symbols k = l mod lanes of each segment): sub-stream b * lanes + l lands in the last nwords[b * lanes + l]
-    words of slab b * lanes + l; status is per stream ([nstreams])"""
-    name = "rans_encode_lanes"
-    nsub = _rans_lanes(lanes, nstreams, name)
-    if cap_words <= 0:
-        raise ValueError(f"{name}: cap_words = {cap_words} must be positive")
-    _rans_buf(symbols, torch.int32, 1, name, "symbols")
-    _rans_buf(indexes, torch.int32, 1, name, "indexes")
-    _rans_buf(slabs, torch.int32, nsub * cap_words, name, "slabs")
-    _rans_buf(nwords, torch.int32, nsub, name, "nwords")
-    _rans_buf(status, torch.int32, nstreams, name, "status")
-    _rans_on_device(name, symbols=symbols, indexes=indexes, slabs=slabs, nwords=nwords, status=status)
-    _lib.call("tmae_rans_encode_lanes", _p(symbols), sym_strides[0], sym_strides[1], _p(indexes), idx_strides[0],
-              idx_strides[1], nstreams, nseg, seg_len, *_rans_tables(tables), _p(slabs), cap_words, _p(nwords),
-              _p(status), lanes, _stream())
+    _rans_decode("rans_decode_streams", None, words, total_words, word_offsets, word_counts, indexes, idx_strides,
+                 symbols, sym_strides, nstreams, seg0, nseg, seg_len, tables, state, pos, status, first)
 
 
 def rans_decode_lanes(words, total_words, word_offsets, word_counts, indexes, idx_strides, symbols, sym_strides,
                       nstreams, seg0, nseg, seg_len, tables, state, pos, status, first, lanes):
     """rans_decode_streams of lane-interleaved streams: word_offsets / word_counts / state / pos are per sub-stream
     ([nstreams * lanes], stream-major), status per stream"""
-    name = "rans_decode_lanes"
-    nsub = _rans_lanes(lanes, nstreams, name)
-    _rans_buf(words, torch.int32, max(int(total_words), 1), name, "words")
-    _rans_buf(word_offsets, torch.int64, nsub, name, "word_offsets")
-    _rans_buf(word_counts, torch.int32, nsub, name, "word_counts")
-    _rans_buf(indexes, torch.int32, 1, name, "indexes")
-    _rans_buf(symbols, torch.int32, 1, name, "symbols")
-    _rans_buf(state, torch.int64, nsub, name, "state")
-    _rans_buf(pos, torch.int32, nsub, name, "pos")
-    _rans_buf(status, torch.int32, nstreams, name, "status")
-    _rans_on_device(name, words=words, word_offsets=word_offsets, word_counts=word_counts, indexes=indexes,
-                    symbols=symbols, state=state, pos=pos, status=status)
-    _lib.call("tmae_rans_decode_lanes", _p(words), total_words, _p(word_offsets), _p(word_counts), _p(indexes),
-              idx_strides[0], idx_strides[1], _p(symbols), sym_strides[0], sym_strides[1], nstreams, seg0, nseg,
-              seg_len, *_rans_tables(tables), _p(state), _p(pos), _p(status), int(bool(first)), lanes, _stream())
+    _rans_decode("rans_decode_lanes", lanes, words, total_words, word_offsets, word_counts, indexes, idx_strides,
+                 symbols, sym_strides, nstreams, seg0, nseg, seg_len, tables, state, pos, status, first)
 
 
 def _eb_params(eb) -> EBParams:

@@ -333,6 +333,17 @@ int tmae_eb_dequantize(const int* symbols, const tmae_eb_params* params, float* 
 /* inverse[b][perm[b][j]] = j (ids_shuffle from ids_restore for MCM.decompress) */
 int tmae_invert_permutation(const int64_t* perm, int64_t* inverse, int n, int L, void* stream);
 
+/* ---- side information of the per-image bitstream (csrc/ids_pack.hip; format: DESIGN.md, bitstream.py) ----
+ * The kept ids ids_shuffle[b][0..K) as K fields of bits = max(1, ceil(log2 L)) bits, LSB first, in
+ * W = ceil(K * bits / 32) little-endian words per image (tail bits zero); 1 <= K <= L <= 1024.
+ * pack: ids_shuffle [n][L] i64 -> words [n][W]. */
+int tmae_ids_pack(const int64_t* ids_shuffle, uint32_t* words, int n, int L, int K, void* stream);
+/* unpack: words [n][W] -> ids_shuffle, ids_restore [n][L] i64 (the kept ids, then the unused ones ascending, and
+ * the inverse) and status [n]: 0 ok, 1 id >= L, 2 duplicate id, 3 non-zero tail bits.  An image with a non-zero
+ * status gets the identity permutation in both outputs, so nothing downstream can index outside its rows. */
+int tmae_ids_unpack(const uint32_t* words, int64_t* ids_shuffle, int64_t* ids_restore, int* status, int n, int L,
+                    int K, void* stream);
+
 /* ---------------------------------------------------------------- entropy coding (host, no device work)
  * compressai 1.2.4's coder restated (csrc/rans.cpp; not vendored in the reference): 64-bit rANS, 16-bit
  * precision, bypass-escaped tails.  CDF tables are int32 [ncdf][cdf_stride] rows with cdf_sizes[c] valid

@@ -156,6 +156,9 @@ SIGNATURES = {
     "tmae_eb_symbols": [P, ctypes.POINTER(EBParams), P, I, I, I, P, P],
     "tmae_eb_dequantize": [P, ctypes.POINTER(EBParams), P, I, I, I, P, I, P],
     "tmae_invert_permutation": [P, P, I, I, P],
+    # side information of the per-image bitstream (csrc/ids_pack.hip)
+    "tmae_ids_pack": [P, P, I, I, I, P],
+    "tmae_ids_unpack": [P, P, P, P, I, I, I, P],
     "tmae_pmf_to_quantized_cdf": [P, I, I, P],
     "tmae_rans_encoder_create": [ctypes.POINTER(ctypes.c_void_p)],
     "tmae_rans_encode_with_indexes": [P, P, P, LL, P, I, P, P, I],

@@ -1,0 +1,185 @@
+"""Self-contained per-image bitstream, container version 1 (DESIGN.md "Container format"): the host part.
+
+One blob per image carries everything ``MCM.decode_bytes`` needs.  Little-endian, a whole number of 32-bit words:
+
+    bytes 0-3    b"TMC" + version byte 1
+          4-5    img_size u16
+          6-7    num_keep_patches K u16
+          8      patch_size u8
+          9      low nibble log2(lanes), high nibble log2(z_lanes)
+          10-11  length of the z record in 32-bit words, u16
+          12-13  original width u16, 14-15 original height u16 (0, 0 = not recorded)
+          then   W = ceil(K * bits / 32) words of kept ids
+          then   the z record, then the y record (the rest of the blob)
+
+L = (img_size / patch_size)^2 and bits = max(1, ceil(log2 L)).  Id k (= ids_shuffle[k], the patch token k came
+from) occupies bits [k * bits, (k + 1) * bits) of the id section's bit string, LSB first; bit i of the string is
+bit i % 32 of word i / 32; unused tail bits are zero.  The records are the strings ``MCM.compress_batch`` returns:
+the plain rANS stream at one lane, the ``coder.encode_record`` record at more.
+
+``pack_ids_host`` / ``unpack_ids_host`` restate the two device kernels (csrc/ids_pack.hip) in numpy; the tests use
+them as the oracle.  Nothing here touches the device.
+"""
+from __future__ import annotations
+
+import struct
+from typing import NamedTuple
+
+import numpy as np
+
+MAGIC = b"TMC"
+VERSION = 1
+HEADER_BYTES = 16
+MAX_L = 1024       # IDS_MAXL of the kernels
+MAX_LANE_LOG2 = 6  # lanes <= 64 (coder.check_lanes)
+_HEADER = struct.Struct("<3sBHHBBHHH")
+
+# status words of unpack (tmae_ids_unpack)
+IDS_STATUS = {1: "patch id outside the image", 2: "duplicate patch id", 3: "non-zero padding bits"}
+
+
+class Blob(NamedTuple):
+    """parse()'s result: the header fields, then views of the three sections"""
+    img_size: int
+    num_keep_patches: int
+    patch_size: int
+    lanes: int
+    z_lanes: int
+    orig_size: tuple | None  # (width, height) or None when not recorded
+    ids: np.ndarray          # uint32 [W] view
+    z: memoryview
+    y: memoryview
+
+    @property
+    def num_patches(self) -> int:
+        return (self.img_size // self.patch_size) ** 2
+
+
+def id_bits(L: int) -> int:
+    """bits of one packed id: max(1, ceil(log2 L))"""
+    return max(1, (int(L) - 1).bit_length())
+
+
+def id_words(L: int, K: int) -> int:
+    """32-bit words of the id section: ceil(K * bits / 32)"""
+    return (int(K) * id_bits(L) + 31) // 32
+
+
+def _log2_lanes(lanes, name):
+    v = int(lanes)
+    if v < 1 or v & (v - 1) or v > 1 << MAX_LANE_LOG2:
+        raise ValueError(f"{name} = {lanes!r} must be a power of two in 1..{1 << MAX_LANE_LOG2}")
+    return v.bit_length() - 1
+
+
+def _check_geometry(img_size, K, patch):
+    if patch < 1 or img_size < 1 or img_size % patch:
+        raise ValueError(f"patch_size {patch} does not divide img_size {img_size}")
+    L = (img_size // patch) ** 2
+    if L > MAX_L:
+        raise ValueError(f"{L} patches: the format holds at most {MAX_L}")
+    if not 1 <= K <= L:
+        raise ValueError(f"num_keep_patches {K} outside 1..{L} (the number of patches)")
+    return L
+
+
+def pack_header(img_size, num_keep_patches, patch_size, lanes=1, z_lanes=1, z_words=0, orig_size=None) -> bytes:
+    """the 16 header bytes; z_words = length of the z record in 32-bit words, orig_size = (width, height) or None"""
+    img_size, K, patch, z_words = int(img_size), int(num_keep_patches), int(patch_size), int(z_words)
+    if not (0 < img_size < 1 << 16 and 0 < patch < 1 << 8):
+        raise ValueError(f"img_size {img_size} / patch_size {patch} do not fit the header (u16 / u8)")
+    _check_geometry(img_size, K, patch)
+    if not 0 <= z_words < 1 << 16:
+        raise ValueError(f"z record of {z_words} words does not fit the header's u16")
+    w, h = (0, 0) if orig_size is None else (int(orig_size[0]), int(orig_size[1]))
+    if not (0 <= w < 1 << 16 and 0 <= h < 1 << 16):
+        raise ValueError(f"original size {(w, h)} does not fit the header's u16 fields")
+    nib = _log2_lanes(lanes, "lanes") | _log2_lanes(z_lanes, "z_lanes") << 4
+    return _HEADER.pack(MAGIC, VERSION, img_size, K, patch, nib, z_words, w, h)
+
+
+def assemble(img_size, num_keep_patches, patch_size, lanes, z_lanes, orig_size, ids_words, z_record, y_record) -> bytes:
+    """one blob from its parts; ids_words: uint32-compatible [W] array (pack_ids_host / ops.ids_pack of one image)"""
+    L = _check_geometry(int(img_size), int(num_keep_patches), int(patch_size))
+    ids = np.ascontiguousarray(ids_words).view(np.uint32).reshape(-1).astype("<u4", copy=False)
+    if ids.size != id_words(L, num_keep_patches):
+        raise ValueError(f"{ids.size} id words, {id_words(L, num_keep_patches)} expected")
+    z, y = bytes(z_record), bytes(y_record)
+    if len(z) % 4 or len(y) % 4:
+        raise ValueError(f"records are whole 32-bit words (z {len(z)} bytes, y {len(y)} bytes)")
+    return pack_header(img_size, num_keep_patches, patch_size, lanes, z_lanes, len(z) // 4, orig_size) \
+        + ids.tobytes() + z + y
+
+
+def parse(blob) -> Blob:
+    """header fields and views of the id words, the z record and the y record; ValueError on a blob that is not a
+    well-formed version-1 container (the records themselves are checked by the coder)"""
+    mv = memoryview(blob).cast("B") if not isinstance(blob, memoryview) else blob.cast("B")
+    n = len(mv)
+    if n < HEADER_BYTES:
+        raise ValueError(f"{n} bytes: shorter than the {HEADER_BYTES}-byte header")
+    magic, version, img_size, K, patch, nib, z_words, w, h = _HEADER.unpack_from(mv, 0)
+    if magic != MAGIC:
+        raise ValueError(f"not a TMC bitstream (magic {bytes(magic)!r})")
+    if version != VERSION:
+        raise ValueError(f"container version {version}, this reader knows version {VERSION}")
+    if n % 4:
+        raise ValueError(f"{n} bytes: not a whole number of 32-bit words")
+    ll, zl = nib & 15, nib >> 4
+    if ll > MAX_LANE_LOG2 or zl > MAX_LANE_LOG2:
+        raise ValueError(f"lane fields 2^{ll} / 2^{zl}: at most 2^{MAX_LANE_LOG2} lanes")
+    L = _check_geometry(img_size, K, patch)
+    W = id_words(L, K)
+    need = HEADER_BYTES + 4 * (W + z_words + 2)
+    if n < need:
+        raise ValueError(f"{n} bytes: header + {W} id words + {z_words} z words + at least 2 y words take {need}")
+    z0 = HEADER_BYTES + 4 * W
+    y0 = z0 + 4 * z_words
+    ids = np.frombuffer(mv, dtype="<u4", count=W, offset=HEADER_BYTES)
+    return Blob(img_size, K, patch, 1 << ll, 1 << zl, (w, h) if (w, h) != (0, 0) else None, ids, mv[z0:y0], mv[y0:])
+
+
+def pack_ids_host(ids_keep, L: int) -> np.ndarray:
+    """ids_keep [K] or [n, K] (each id in [0, L)) -> uint32 words [W] or [n, W]: tmae_ids_pack in numpy"""
+    ids = np.asarray(ids_keep, dtype=np.int64)
+    one = ids.ndim == 1
+    ids = np.atleast_2d(ids)
+    n, K = ids.shape
+    bits = id_bits(L)
+    if not 1 <= K <= L or (ids < 0).any() or (ids >= L).any():
+        raise ValueError(f"pack_ids_host: need 1 <= K={K} <= L={L} and every id in [0, L)")
+    W = id_words(L, K)
+    # the bit string, one byte per bit, LSB of id k at position k * bits
+    string = np.zeros((n, 32 * W), dtype=np.uint8)
+    string[:, :K * bits] = ((ids[:, :, None] >> np.arange(bits)) & 1).reshape(n, K * bits)
+    words = (string.reshape(n, W, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    return words[0] if one else words
+
+
+def unpack_ids_host(words, L: int, K: int):
+    """words uint32 [W] or [n, W] -> (ids_shuffle, ids_restore int64 [L] or [n, L], status int32 scalar or [n]):
+    tmae_ids_unpack in numpy.  The kept ids, then the unused ones ascending; status 0 ok, 1 id >= L, 2 duplicate id,
+    3 non-zero tail bits (the lowest that applies), and the identity in both outputs wherever it is not 0."""
+    w = np.asarray(words).astype(np.uint32, copy=False)
+    one = w.ndim == 1
+    w = np.atleast_2d(w)
+    n, bits = w.shape[0], id_bits(L)
+    if not 1 <= K <= L or w.shape[1] != id_words(L, K):
+        raise ValueError(f"unpack_ids_host: need 1 <= K={K} <= L={L} and {id_words(L, K)} words per image")
+    string = ((w[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(n, -1).astype(np.int64)
+    ids = (string[:, :K * bits].reshape(n, K, bits) << np.arange(bits)).sum(axis=2)
+    shuf = np.tile(np.arange(L, dtype=np.int64), (n, 1))
+    rest = shuf.copy()
+    status = np.zeros(n, dtype=np.int32)
+    for b in range(n):
+        if (ids[b] >= L).any():
+            status[b] = 1
+        elif np.unique(ids[b]).size != K:
+            status[b] = 2
+        elif string[b, K * bits:].any():
+            status[b] = 3
+        else:
+            unused = np.setdiff1d(np.arange(L), ids[b])  # ascending
+            shuf[b] = np.concatenate([ids[b], unused])
+            rest[b, shuf[b]] = np.arange(L)
+    return (shuf[0], rest[0], status[0]) if one else (shuf, rest, status)

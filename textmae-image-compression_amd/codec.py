@@ -1,0 +1,102 @@
+"""Command-line codec on the self-contained bitstreams (bitstream.py, MCM.encode_bytes / decode_bytes):
+
+    python -m textmae_amd.codec encode -c CKPT -d FOLDER -o OUT [--lanes N --batch B]
+    python -m textmae_amd.codec decode -c CKPT -d OUT -o PNGS [--original_size]
+
+``encode`` reads FOLDER through ``data.ImageFolderLoader`` (the test transform: bicubic resize to the model's
+size, scores from ``<FOLDER>_scores/test.pt`` or the device producer) and writes one ``<name>.tmc`` per image,
+which records the image's original size.  ``decode`` needs only the checkpoint and those files: the geometry
+(input size, kept patches) comes from the first file's header, and every file is checked against the model.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from pathlib import Path
+
+import torch
+
+from . import bitstream
+from .data import ImageFolderLoader
+from .testing import load_checkpoint, save_output
+
+
+def _model(checkpoint, num_keep_patches, input_size, half):
+    model = load_checkpoint(num_keep_patches, checkpoint, input_size).to("cuda")
+    if half:
+        model.compute_dtype = torch.bfloat16
+    model.update(force=True)
+    return model
+
+
+@torch.no_grad()
+def encode(args):
+    model = _model(args.checkpoint, args.num_keep_patches, args.input_size, args.half)
+    loader = ImageFolderLoader(args.dataset, "test", args.batch, size=args.input_size,
+                               patch=model.encoder_embed.patch_size[0])
+    os.makedirs(args.output, exist_ok=True)
+    paths, done, nbytes = loader.imgs_path, 0, 0
+    for imgs, ori_shapes, scores in loader:  # unshuffled: batch i holds paths[done : done + B]
+        blobs = model.encode_bytes(imgs, scores, lanes=args.lanes, orig_sizes=ori_shapes)
+        for p, blob in zip(paths[done:done + len(blobs)], blobs):
+            with open(os.path.join(args.output, p.stem + ".tmc"), "wb") as f:
+                f.write(blob)
+            nbytes += len(blob)
+        done += len(blobs)
+    print(f"{done} images -> {args.output}: {nbytes} bytes, "
+          f"{8.0 * nbytes / (done * args.input_size ** 2):.4f} bpp at {args.input_size}^2")
+    return done
+
+
+@torch.no_grad()
+def decode(args):
+    files = sorted(Path(args.dataset).glob("*.tmc"))
+    if not files:
+        print(f"Error: no .tmc files found in {args.dataset}.", file=sys.stderr)
+        sys.exit(1)
+    with open(files[0], "rb") as f:
+        head = bitstream.parse(f.read())
+    model = _model(args.checkpoint, head.num_keep_patches, head.img_size, args.half)
+    os.makedirs(args.output, exist_ok=True)
+    for s in range(0, len(files), args.batch):
+        group = files[s:s + args.batch]
+        blobs = [p.read_bytes() for p in group]
+        try:
+            out = model.decode_bytes(blobs)
+        except ValueError as e:
+            raise ValueError(f"{e} (blobs of this call: {', '.join(p.name for p in group)})") from None
+        for b, p in enumerate(group):
+            size = out["orig_sizes"][b]
+            save_output(out["x_hat"][b], size, p.stem + ".png", args.output, args.original_size and size is not None)
+    print(f"{len(files)} images -> {args.output}")
+    return len(files)
+
+
+def setup_args():
+    p = argparse.ArgumentParser(prog="textmae_amd.codec", description=__doc__.split("\n\n")[0])
+    sub = p.add_subparsers(dest="command", required=True)
+    for name in ("encode", "decode"):
+        q = sub.add_parser(name)
+        q.add_argument("-c", "--checkpoint", type=str, required=True)
+        q.add_argument("-d", "--dataset", type=str, required=True,
+                       help="image folder (encode) / folder of .tmc files (decode)")
+        q.add_argument("-o", "--output", type=str, required=True)
+        q.add_argument("--batch", type=int, default=16, help="images per device call")
+        q.add_argument("--half", action="store_true", help="bf16 operands; encoder and decoder must agree")
+    q = sub.choices["encode"]
+    q.add_argument("--lanes", type=int, default=1, choices=[1, 2, 4, 8, 16, 32, 64], help="interleaved y lanes")
+    q.add_argument("--num_keep_patches", type=int, default=144)
+    q.add_argument("--input_size", type=int, default=224)
+    sub.choices["decode"].add_argument("--original_size", action="store_true",
+                                       help="save each output resized to the size its file recorded")
+    return p
+
+
+def main(argv):
+    args = setup_args().parse_args(argv)
+    return encode(args) if args.command == "encode" else decode(args)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -366,6 +366,9 @@ class DeviceRansDecoder:
             ops.rans_decode_lanes(*args, L)
         self._started[r0:r1] = True
 
-    def status(self) -> np.ndarray:
-        """per-record status words (synchronises)"""
-        return self._status.cpu().numpy()
+    def status(self, extra=None) -> np.ndarray:
+        """per-record status words (synchronises); extra: a device int32 vector of further status words to bring
+        down in the same copy, appended to the records'"""
+        if extra is None:
+            return self._status.cpu().numpy()
+        return torch.cat([self._status, extra.reshape(-1)]).cpu().numpy()

@@ -396,6 +396,70 @@ class MCM(CompressionModel):
             ex = self._executor(len(strings[1]), dev)
             return {"x_hat": ex.decompress_batch(strings, shape, ids_restore, lanes, z_lanes)}
 
+    def _geometry(self):
+        """(img_size, patch_size, num_keep_patches, L) as the container header states them"""
+        pe = self.encoder_embed
+        return int(pe.img_size[0]), int(pe.patch_size[0]), int(self.num_keep_patches), int(pe.num_patches)
+
+    def encode_bytes(self, imgs, total_scores, lanes=1, z_lanes=None, orig_sizes=None):
+        """compress_batch into self-contained bitstreams -> list of B bytes objects (bitstream.py, container version
+        1): header (geometry, lanes, original size), the kept patch ids packed on the device (ops.ids_pack, at
+        ceil(log2 L) bits each), then compress_batch's z and y records of the image as they are.  decode_bytes needs
+        nothing else, in this process or another.  orig_sizes: optional list of B (width, height) to record."""
+        from . import bitstream
+
+        B = imgs.shape[0]
+        if orig_sizes is not None and len(orig_sizes) != B:
+            raise ValueError(f"{len(orig_sizes)} original sizes for {B} images")
+        out = self.compress_batch(imgs, total_scores, lanes, z_lanes)
+        lanes, z_lanes = out.get("lanes", (1, 1))
+        img, patch, K, _ = self._geometry()
+        ids = ops.ids_pack(self._exec.last_ids_shuffle, K).cpu().numpy()  # the one extra copy: B * W words
+        y, z = out["string"]
+        return [bitstream.assemble(img, K, patch, lanes, z_lanes, None if orig_sizes is None else orig_sizes[b],
+                                   ids[b], z[b], y[b]) for b in range(B)]
+
+    def decode_bytes(self, blobs):
+        """inverse of encode_bytes -> {"x_hat": [B, 3, S, S], "orig_sizes": [(width, height) or None per image]}.
+        Every header is parsed on the host first: a malformed blob, one of another geometry (img_size, patch_size,
+        num_keep_patches) than this model's, or blobs of one call that disagree in their lanes raise ValueError
+        naming the blob's index before anything is launched.  The id words then go up, ops.ids_unpack validates and
+        completes them into ids_restore on the device, and the records take the decompress_batch path; the ids
+        status words are read with the coder's after everything is enqueued, and an image whose side information is
+        corrupt (decoded harmlessly with the identity permutation) raises ValueError("side information of image b")."""
+        from . import bitstream
+
+        blobs = list(blobs)
+        if not blobs:
+            raise ValueError("decode_bytes: no blobs")
+        img, patch, K, L = self._geometry()
+        parsed = []
+        for i, blob in enumerate(blobs):
+            try:
+                p = bitstream.parse(blob)
+            except ValueError as e:
+                raise ValueError(f"blob {i}: {e}") from None
+            if (p.img_size, p.patch_size, p.num_keep_patches) != (img, patch, K):
+                raise ValueError(f"blob {i}: coded for img_size {p.img_size}, patch_size {p.patch_size}, "
+                                 f"num_keep_patches {p.num_keep_patches}; this model has {img}, {patch}, {K}")
+            if parsed and (p.lanes, p.z_lanes) != (parsed[0].lanes, parsed[0].z_lanes):
+                raise ValueError(f"blob {i}: lanes ({p.lanes}, {p.z_lanes}) differ from blob 0's "
+                                 f"({parsed[0].lanes}, {parsed[0].z_lanes}): decode them in separate calls")
+            parsed.append(p)
+        self.entropy_bottleneck._check_cdf()
+        self.gaussian_conditional._check_cdf()
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise ValueError("MCM.decode_bytes runs on the MI355X kernels: move the model to the GPU")
+        strings = [[bytes(p.y) for p in parsed], [bytes(p.z) for p in parsed]]
+        words = torch.from_numpy(np.stack([p.ids for p in parsed]).view(np.int32)).to(dev)
+        with torch.no_grad():
+            ex = self._executor(len(parsed), dev)
+            _, rest, status = ops.ids_unpack(words, L, K)
+            x_hat = ex.decompress_batch(strings, torch.Size([ex.hz, ex.hz]), rest, parsed[0].lanes,
+                                        parsed[0].z_lanes, ids_status=status)
+        return {"x_hat": x_hat, "orig_sizes": [p.orig_size for p in parsed]}
+
 
 class _LazyStreams(collections.abc.Mapping):
     """_Executor.last_streams of compress_batch: the keys compress sets, as host arrays copied from the device on
@@ -725,6 +789,7 @@ class _Executor:
         N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
         eb = m.entropy_bottleneck
         shuf, rest = self._front(self._check_imgs(imgs), scores)
+        self.last_ids_shuffle = shuf  # encode_bytes packs its kept ids as the blobs' side information
         # z: symbols round(z - median); z_hat = symbols + median (= EB.decompress of its own strings)
         ops.eb_likelihood(eb, self.Z, B, N, hz * hz, lik=self.ZLIK, zhat=self.ZHAT, table=self.eb_table)
         zsym = ops.eb_symbols(eb, self.Z, B, N, hz * hz, table=self.eb_table)
@@ -766,10 +831,12 @@ class _Executor:
             zidx = self._zidx = torch.from_numpy(zidx).to(self.device)
         return zidx
 
-    def decompress_batch(self, strings, shape, ids_restore, lanes=1, z_lanes=1):
+    def decompress_batch(self, strings, shape, ids_restore, lanes=1, z_lanes=1, ids_status=None):
         """decompress of per-image records: every string goes up in one copy, the z and y streams are decoded by
         device kernels (the y streams inside the slice loop, one call per slice step), and nothing synchronises with
-        the host until the status words are read after the last kernel of _back has been enqueued"""
+        the host until the status words are read after the last kernel of _back has been enqueued.  ids_status
+        (decode_bytes): ops.ids_unpack's device status words of ids_restore, read in that same copy"""
+        from .bitstream import IDS_STATUS
         from .coder import DeviceRansDecoder, _raise_status
 
         m, B = self.m, self.batch
@@ -804,9 +871,12 @@ class _Executor:
         self._slices(step)
         shuf = ops.invert_permutation(rest)
         x_hat = self._back(shuf, m.encoder_embed.proj.in_channels)
-        status = dec.status()  # the only synchronisation: after everything is enqueued
+        status = dec.status(ids_status)  # the only synchronisation: after everything is enqueued
+        for b in np.flatnonzero(status[2 * B:]):
+            c = int(status[2 * B + b])
+            raise ValueError(f"side information of image {int(b)}: {IDS_STATUS.get(c, f'status {c}')}")
         _raise_status(status[:B], "y stream of image")
-        _raise_status(status[B:], "z stream of image")
+        _raise_status(status[B:2 * B], "z stream of image")
         return x_hat
 
     def encode(self, imgs, scores):

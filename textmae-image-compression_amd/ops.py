@@ -21,7 +21,7 @@ __all__ = [
     "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "mha_plan", "mha_force_stream", "dtype_code", "gc_slices_code", "gc_indexes",
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
-    "rans_encode_lanes", "rans_decode_lanes",
+    "rans_encode_lanes", "rans_decode_lanes", "ids_pack", "ids_unpack",
     "resize_tables", "resize_u8", "rgb_to_gray_u8",
     "mae_loss", "TMAE_F32", "TMAE_BF16", "ACT_NONE", "ACT_GELU",
 ]
@@ -539,6 +539,42 @@ def invert_permutation(perm):
     inv = torch.empty_like(p)
     _lib.call("tmae_invert_permutation", p.data_ptr(), inv.data_ptr(), n, L, _stream())
     return inv
+
+
+def ids_pack(ids_shuffle, K: int):
+    """ids_shuffle int64 [n, L] -> the first K ids of every row packed at max(1, ceil(log2 L)) bits each, LSB first:
+    int32 [n, bitstream.id_words(L, K)] holding the container's little-endian words (bitstream.pack_ids_host on the
+    device)"""
+    from .bitstream import id_words
+
+    s = _need(ids_shuffle, torch.int64, "ids_shuffle")
+    n, L = s.shape
+    if not 1 <= K <= L:
+        raise ValueError(f"ids_pack: need 1 <= K={K} <= L={L}")
+    words = torch.empty((n, id_words(L, K)), dtype=torch.int32, device=s.device)
+    _lib.call("tmae_ids_pack", s.data_ptr(), words.data_ptr(), n, L, int(K), _stream())
+    return words
+
+
+def ids_unpack(words, L: int, K: int):
+    """inverse of ids_pack with validation: words int32 [n, bitstream.id_words(L, K)] -> (ids_shuffle, ids_restore
+    int64 [n, L], status int32 [n]).  The kept ids come first, the unused ones follow in ascending order; status 0 ok,
+    1 id >= L, 2 duplicate id, 3 non-zero tail bits, and an image with a non-zero status gets the identity in both
+    outputs.  Nothing synchronises: the caller reads status when it suits it."""
+    from .bitstream import id_words
+
+    w = _need(words, torch.int32, "words")
+    if not 1 <= K <= L:
+        raise ValueError(f"ids_unpack: need 1 <= K={K} <= L={L}")
+    if w.dim() != 2 or w.shape[1] != id_words(L, K):
+        raise ValueError(f"ids_unpack: words must be [n, {id_words(L, K)}] for L={L}, K={K}, got {tuple(w.shape)}")
+    n = w.shape[0]
+    shuf = torch.empty((n, L), dtype=torch.int64, device=w.device)
+    rest = torch.empty_like(shuf)
+    status = torch.empty(n, dtype=torch.int32, device=w.device)
+    _lib.call("tmae_ids_unpack", w.data_ptr(), shuf.data_ptr(), rest.data_ptr(), status.data_ptr(), n, int(L), int(K),
+              _stream())
+    return shuf, rest, status
 
 
 def rans_stream_cap_words(nsymbols: int) -> int:

@@ -10,6 +10,9 @@ Same function names and arithmetic as the reference (testing.py:40-165, 199-250)
   * batch 1, the test transform (PIL bicubic resize to 224, ToTensor; no normalisation,
     utils/dataloader.py:69-73), scores from <dataset>_scores/test.pt or, when absent, from the device
     score-map producer (scores.py) instead of the reference's RuntimeError (dataloader.py:30-31).
+``--bitstream DIR`` (no reference counterpart) sends every image through a self-contained file ``DIR/<name>.tmc``
+(MCM.encode_bytes, written, read back, MCM.decode_bytes) and reports the files' own bpp, 8 * size / pixels, which
+counts the container header and the side information in full.
 Deviation: ``inference_entropy_estimation`` takes the scores (the reference calls model.forward(x) without
 them, testing.py:106, which raises).
 """
@@ -106,6 +109,37 @@ def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None,
 
 
 @torch.no_grad()
+def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_dir, output_dir=None, lanes=None,
+                        original_size=False):
+    """--bitstream DIR: encode_bytes -> DIR/<name>.tmc -> read the file back -> decode_bytes.  The bpp is that of
+    the file, 8 * size / pixels: header and side information counted in full.  original_size takes the size the
+    blob itself recorded."""
+    device = next(model.parameters()).device
+    x = x.to(device)
+    total_score = total_score.to(device)
+    path = os.path.join(bitstream_dir, Path(file_name).stem + ".tmc")
+    torch.cuda.synchronize()
+    start = time.time()
+    blobs = model.encode_bytes(x, total_score, lanes=1 if lanes is None else lanes,
+                               orig_sizes=[(int(ori_shape[0]), int(ori_shape[1]))])
+    enc_time = time.time() - start
+    with open(path, "wb") as f:
+        f.write(blobs[0])
+    with open(path, "rb") as f:
+        blob = f.read()
+    start = time.time()
+    out_dec = model.decode_bytes([blob])
+    torch.cuda.synchronize()
+    dec_time = time.time() - start
+    metrics = compute_metrics(x, out_dec["x_hat"], 255)
+    num_pixels = x.size(0) * x.size(2) * x.size(3)
+    if output_dir is not None:
+        save_output(out_dec["x_hat"], out_dec["orig_sizes"][0], file_name, output_dir, original_size)
+    return {"psnr": metrics["psnr"], "ms-ssim": metrics["ms-ssim"], "bpp": 8.0 * os.path.getsize(path) / num_pixels,
+            "encoding_time": enc_time, "decoding_time": dec_time}
+
+
+@torch.no_grad()
 def inference_entropy_estimation(model, x, total_score):
     """testing.py:103-120 with the scores passed (the reference omits them and raises)"""
     device = next(model.parameters()).device
@@ -142,15 +176,23 @@ def load_test_images(paths, size=224, device=None):
 
 
 def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False, lanes=None,
-               original_size=False):
-    """testing.py:128-165 over pre-loaded (img [1,3,S,S], orig_shape) pairs and a [N, L] score tensor"""
+               original_size=False, bitstream_dir=None):
+    """testing.py:128-165 over pre-loaded (img [1,3,S,S], orig_shape) pairs and a [N, L] score tensor; with
+    bitstream_dir every image goes through its .tmc file there (inference_bitstream; needs names)"""
     metrics = defaultdict(float)
     if output_dir is not None:
         os.makedirs(output_dir, exist_ok=True)
+    if bitstream_dir is not None:
+        if names is None:
+            raise ValueError("eval_model: bitstream_dir needs the images' names")
+        os.makedirs(bitstream_dir, exist_ok=True)
     for i, (img, ori_shape) in enumerate(images):
         ts = scores[i:i + 1]
         if entropy_estimation:
             rv = inference_entropy_estimation(model, img, ts)
+        elif bitstream_dir is not None:
+            rv = inference_bitstream(model, img, ori_shape, ts, names[i], bitstream_dir, output_dir, lanes=lanes,
+                                     original_size=original_size)
         else:
             rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir, lanes=lanes,
                            original_size=original_size)
@@ -191,6 +233,9 @@ def setup_args():
                    help="code on the device (compress_batch / decompress_batch) with this many interleaved y lanes")
     p.add_argument("--original_size", action="store_true",
                    help="save each output resized back to its image's original size (bicubic, on the device)")
+    p.add_argument("--bitstream", type=str, default=None, metavar="DIR",
+                   help="code every image into the self-contained file DIR/<name>.tmc (encode_bytes, --lanes y lanes, "
+                        "default 1), read it back and decode that (decode_bytes); bpp = 8 * file size / pixels")
     return p
 
 
@@ -216,10 +261,12 @@ def main(argv):
             model.compute_dtype = torch.bfloat16
         model.update(force=True)
         m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths], args.entropy_estimation,
-                       lanes=args.lanes, original_size=args.original_size)
+                       lanes=args.lanes, original_size=args.original_size, bitstream_dir=args.bitstream)
         for k, v in m.items():
             results[k].append(v)
     desc = "entropy estimation" if args.entropy_estimation else args.entropy_coder
+    if args.bitstream is not None and not args.entropy_estimation:
+        desc += "; bpp of the .tmc files: header and side information counted in full"
     output = {"name": "MCM", "description": f"Inference ({desc})", "results": results}
     print(json.dumps(output, indent=2))
     os.makedirs(args.output_path, exist_ok=True)

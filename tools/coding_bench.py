@@ -7,8 +7,11 @@ process; each timed call is a wall clock around a device synchronise (both paths
 status read anyway).  Prints ONE JSON line: medians and spread (min, max, interquartile range) of both paths per
 batch, and the bytes per image of both formats.  --lanes 1,4,16,64 adds one device column per value above 1
 (compress_batch(lanes=N), lane-interleaved records; 1 is the plain device column), alternating with the others.
+--bitstream adds, beside every device column, a "bytes" column: MCM.encode_bytes + decode_bytes at the same lanes (the
+self-contained blobs: compress_batch's records behind a header and the packed kept ids), the mean blob size split
+into header, ids, z and y, and whether either call is slower than its device column by more than the spread.
 
-    python tools/coding_bench.py [--rounds 10] [--warmup 3] [--batches 64,1] [--lanes 1,4,16,64]
+    python tools/coding_bench.py [--rounds 10] [--warmup 3] [--batches 64,1] [--lanes 1,4,16,64] [--bitstream]
                                  [--out profiles/coding_device/x.json]
 """
 import argparse
@@ -48,7 +51,18 @@ def stats(ms):
             "iqr_ms": round(q[2] - q[0], 3), "n": len(ms)}
 
 
-def run_batch(model, batch, img, rounds, warmup, dev, lanes=()):
+def blob_split(blobs):
+    """mean bytes per blob of each section"""
+    from textmae_amd import bitstream
+
+    parts = [bitstream.parse(b) for b in blobs]
+    n = len(parts)
+    return {"header": bitstream.HEADER_BYTES, "ids": round(sum(4 * p.ids.size for p in parts) / n, 1),
+            "z": round(sum(len(p.z) for p in parts) / n, 1), "y": round(sum(len(p.y) for p in parts) / n, 1),
+            "total": round(sum(len(b) for b in blobs) / n, 1)}
+
+
+def run_batch(model, batch, img, rounds, warmup, dev, lanes=(), bitstream=False):
     L = model.encoder_embed.num_patches
     x, s = inputs(batch, img, L, 1000, dev)
     paths = {
@@ -62,8 +76,14 @@ def run_batch(model, batch, img, rounds, warmup, dev, lanes=()):
             paths[f"device_l{n}"] = (lambda n=n: model.compress_batch(x, s, lanes=n),
                                      lambda c, n=n: model.decompress_batch(c["string"], c["shape"], c["ids_restore"],
                                                                            lanes=n))
+    pairs = {}  # bytes column -> the device column it wraps
+    if bitstream:
+        for n in [1] + [n for n in lanes if n != 1]:
+            name, devname = ("bytes", "device") if n == 1 else (f"bytes_l{n}", f"device_l{n}")
+            paths[name] = (lambda n=n: model.encode_bytes(x, s, lanes=n), lambda c: model.decode_bytes(c))
+            pairs[name] = devname
     t = {f"{p}_{k}": [] for p in paths for k in ("compress", "decompress")}
-    rec, size = {}, {}
+    rec, size, split = {}, {}, {}
     with torch.no_grad():
         for r in range(warmup + rounds):
             for p, (comp, decomp) in paths.items():  # the paths alternate within every round
@@ -72,7 +92,11 @@ def run_batch(model, batch, img, rounds, warmup, dev, lanes=()):
                 if r >= warmup:
                     t[f"{p}_compress"].append(tc)
                     t[f"{p}_decompress"].append(td)
-                rec[p], size[p] = d["x_hat"], sum(len(b) for part in c["string"] for b in part) / batch
+                rec[p] = d["x_hat"]
+                if p in pairs:
+                    size[p], split[p] = sum(len(b) for b in c) / batch, blob_split(c)
+                else:
+                    size[p] = sum(len(b) for part in c["string"] for b in part) / batch
     if not all(torch.equal(rec["host"], rec[p]) for p in paths):
         raise SystemExit("coding_bench: the paths reconstruct different images")
     out = {k: stats(v) for k, v in t.items()}
@@ -89,6 +113,13 @@ def run_batch(model, batch, img, rounds, warmup, dev, lanes=()):
             v = out[f"{p}_total"]
             out[f"{p}_faster_than_host_beyond_spread"] = bool(v["max_ms"] < h["min_ms"])
             out[f"{p}_faster_than_device_beyond_spread"] = bool(v["max_ms"] < d["min_ms"])
+    if pairs:
+        out["blob_bytes_per_image"] = split
+    for p, q in pairs.items():  # slower beyond the spread: the fastest blob round is slower than the slowest device one
+        for k in ("compress", "decompress", "total"):
+            a, b = out[f"{p}_{k}"], out[f"{q}_{k}"]
+            out[f"{p}_{k}_vs_{q}"] = {"median_delta_ms": round(a["median_ms"] - b["median_ms"], 3),
+                                      "slower_beyond_spread": bool(a["min_ms"] > b["max_ms"])}
     return out
 
 
@@ -101,6 +132,8 @@ def main():
     ap.add_argument("--keep", type=int, default=144)
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--lanes", default="", help="comma-separated y lane counts (powers of two up to 64)")
+    ap.add_argument("--bitstream", action="store_true",
+                    help="add encode_bytes / decode_bytes beside every device column")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if args.rounds < 2:
@@ -121,7 +154,7 @@ def main():
     if lanes:
         res["lanes"] = lanes
     for b in (int(v) for v in args.batches.split(",")):
-        res[f"batch_{b}"] = run_batch(model, b, args.img, args.rounds, args.warmup, dev, lanes)
+        res[f"batch_{b}"] = run_batch(model, b, args.img, args.rounds, args.warmup, dev, lanes, args.bitstream)
     line = json.dumps(res)
     print(line)
     if args.out:

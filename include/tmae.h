@@ -474,6 +474,22 @@ int tmae_resize_u8(const unsigned char* src, int n, int H, int W, int Ho, int Wo
  * non-JPEG files (cv2.imread IMREAD_GRAYSCALE through libpng), in front of tmae_image_scores */
 int tmae_rgb_to_gray_u8(const unsigned char* rgb, long long npixels, unsigned char* gray, void* stream);
 
+/* ---- tiled full-resolution coding (csrc/tile.hip; geometry: tiling.py) ----
+ * An H x W image as overlapping S x S tiles: overlap 0 <= O <= S / 2, stride = S - O,
+ * nx = max(1, ceil((W - O) / stride)), ny likewise, T = nx * ny <= 4096, tile t = ty * nx + tx at origin
+ * (ty * stride, tx * stride); a sample outside the image is the nearest edge pixel.
+ * cut: src uint8 [H][W][3] -> tiles f32 [nt][3][S][S] = v / 255 (ToTensor, bitwise torch's) and
+ * gray uint8 [nt][S][S] (tmae_rgb_to_gray_u8's formula) of tiles t0 .. t0 + nt. */
+int tmae_tile_cut_u8(const unsigned char* src, int H, int W, int S, int O, int t0, int nt, float* tiles,
+                     unsigned char* gray, void* stream);
+/* blend: tiles f32 [T][3][S][S] -> out_f32 [3][H][W] and / or out_u8 [H][W][3] (either may be NULL, not both).
+ * Per axis the weight at tile-local i is i + 1 (i < O, a tile before), S - i (i >= S - O, a tile after), else
+ * O + 1; a pixel's value is sum(float(wy * wx) * v) over its covering tiles (ty, then tx ascending) divided by
+ * float((O + 1)^2), all f32 and unfused; a pixel one tile covers is that tile's value bit for bit.
+ * out_u8 = round-half-even(clamp(v, 0, 1) * 255). */
+int tmae_tile_blend(const float* tiles, int H, int W, int S, int O, float* out_f32, unsigned char* out_u8,
+                    void* stream);
+
 /* ---------------------------------------------------------------- VGG16 feature loss (MCM.forward_loss,
  * models/Compression/loss/vgg.py:86-115 with common/image_utils.py:4-23).  The convolutions are tmae_conv3x3
  * (act TMAE_ACT_RELU) and tmae_conv_dgrad; these are the glue kernels, NHWC, dtype = operand type. */

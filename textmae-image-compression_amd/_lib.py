@@ -183,6 +183,9 @@ SIGNATURES = {
     # model inputs: Pillow-exact resize and the score producer's grayscale (csrc/resize.hip)
     "tmae_resize_u8": [P, I, I, I, I, I, P, P, I, P, P, I, I, ctypes.POINTER(F), ctypes.POINTER(F), P, P, LL, P],
     "tmae_rgb_to_gray_u8": [P, LL, P, P],
+    # tiled full-resolution coding (csrc/tile.hip)
+    "tmae_tile_cut_u8": [P, I, I, I, I, I, I, P, P, P],
+    "tmae_tile_blend": [P, I, I, I, I, P, P, P],
     # VGG16 feature loss glue
     "tmae_vgg_prep": [P, I, I, I, I, I, P, I, P],
     "tmae_vgg_prep_bwd": [P, I, I, I, I, I, P, I, P],

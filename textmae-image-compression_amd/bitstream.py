@@ -19,6 +19,10 @@ the plain rANS stream at one lane, the ``coder.encode_record`` record at more.
 
 ``pack_ids_host`` / ``unpack_ids_host`` restate the two device kernels (csrc/ids_pack.hip) in numpy; the tests use
 them as the oracle.  Nothing here touches the device.
+
+A second format, b"TMT" version 1 (``assemble_image`` / ``parse_image`` / ``tile_blob``, layout further down), holds
+one image coded at its own resolution as overlapping tiles: the sections of the tiles' TMC blobs behind one header
+and a table of record lengths (``MCM.encode_image`` / ``decode_image``).
 """
 from __future__ import annotations
 
@@ -137,6 +141,148 @@ def parse(blob) -> Blob:
     y0 = z0 + 4 * z_words
     ids = np.frombuffer(mv, dtype="<u4", count=W, offset=HEADER_BYTES)
     return Blob(img_size, K, patch, 1 << ll, 1 << zl, (w, h) if (w, h) != (0, 0) else None, ids, mv[z0:y0], mv[y0:])
+
+
+# ------------------------------------------------------------------------------------ tiled images: b"TMT", version 1
+# One file per image coded at its own resolution as overlapping model-sized tiles (tiling.py).
+# Little-endian, a whole number of 32-bit words:
+#
+#     bytes 0-3    b"TMT" + version byte 1
+#           4-5    tile size S u16, 6-7 K u16, 8 patch_size u8, 9 lane nibbles (all as in TMC)
+#           10-11  overlap O u16
+#           12-13  image width u16, 14-15 image height u16 (both >= 1)
+#           16-17  chunk u16: the tile batch the encoder used (>= 1)
+#           18-19  zero
+#           20-23  T u32 = nx * ny of the fields above
+#           then   T table entries: z_words u32, y_words u32
+#           then   per tile, in order: W = id_words(L, K) id words, the z record, the y record
+IMAGE_MAGIC = b"TMT"
+IMAGE_VERSION = 1
+IMAGE_HEADER_BYTES = 24
+_IMAGE_HEADER = struct.Struct("<3sBHHBBHHHHHI")
+
+
+class ImageBlob(NamedTuple):
+    """parse_image()'s result: the header fields, then per tile views of the id words, the z and the y record"""
+    img_size: int            # the tile size S
+    num_keep_patches: int
+    patch_size: int
+    lanes: int
+    z_lanes: int
+    overlap: int
+    width: int
+    height: int
+    chunk: int
+    ids: list                # T uint32 [W] views
+    z: list                  # T memoryviews
+    y: list
+
+    @property
+    def num_patches(self) -> int:
+        return (self.img_size // self.patch_size) ** 2
+
+    @property
+    def num_tiles(self) -> int:
+        return len(self.ids)
+
+
+def assemble_image(img_size, num_keep_patches, patch_size, lanes, z_lanes, overlap, width, height, chunk, ids_words,
+                   z_records, y_records) -> bytes:
+    """one TMT file from its parts; ids_words: uint32-compatible [T, W] (ops.ids_pack of the tiles), z_records /
+    y_records: T byte strings each (compress_batch's records of the tiles, in tile order)"""
+    from .tiling import grid
+
+    img_size, K, patch = int(img_size), int(num_keep_patches), int(patch_size)
+    overlap, width, height, chunk = int(overlap), int(width), int(height), int(chunk)
+    if not (0 < img_size < 1 << 16 and 0 < patch < 1 << 8):
+        raise ValueError(f"img_size {img_size} / patch_size {patch} do not fit the header (u16 / u8)")
+    L = _check_geometry(img_size, K, patch)
+    if not (1 <= width < 1 << 16 and 1 <= height < 1 << 16):
+        raise ValueError(f"image size {(width, height)} does not fit the header's u16 fields (both >= 1)")
+    if not 1 <= chunk < 1 << 16:
+        raise ValueError(f"chunk {chunk} outside 1..65535")
+    g = grid(height, width, img_size, overlap)
+    W = id_words(L, K)
+    ids = np.ascontiguousarray(ids_words).view(np.uint32).reshape(-1, W).astype("<u4", copy=False)
+    if not ids.shape[0] == len(z_records) == len(y_records) == g.T:
+        raise ValueError(f"{ids.shape[0]} id rows, {len(z_records)} z and {len(y_records)} y records for {g.T} tiles")
+    table, body = [], []
+    for t in range(g.T):
+        z, y = bytes(z_records[t]), bytes(y_records[t])
+        if len(z) % 4 or len(y) % 4 or len(z) < 8 or len(y) < 8:
+            raise ValueError(f"tile {t}: records are whole 32-bit words, at least 2 (z {len(z)} bytes, y {len(y)} "
+                             f"bytes)")
+        table.append(struct.pack("<II", len(z) // 4, len(y) // 4))
+        body += [ids[t].tobytes(), z, y]
+    nib = _log2_lanes(lanes, "lanes") | _log2_lanes(z_lanes, "z_lanes") << 4
+    head = _IMAGE_HEADER.pack(IMAGE_MAGIC, IMAGE_VERSION, img_size, K, patch, nib, overlap, width, height, chunk, 0,
+                              g.T)
+    return head + b"".join(table) + b"".join(body)
+
+
+def parse_image(blob) -> ImageBlob:
+    """header fields and per-tile views of a TMT file; ValueError on anything that is not a well-formed version-1
+    file (the records themselves are checked by the coder)"""
+    from .tiling import MAX_TILES, grid
+
+    mv = memoryview(blob).cast("B") if not isinstance(blob, memoryview) else blob.cast("B")
+    n = len(mv)
+    if n < IMAGE_HEADER_BYTES:
+        raise ValueError(f"{n} bytes: shorter than the {IMAGE_HEADER_BYTES}-byte header")
+    magic, version, S, K, patch, nib, O, width, height, chunk, zero, T = _IMAGE_HEADER.unpack_from(mv, 0)
+    if magic != IMAGE_MAGIC:
+        raise ValueError(f"not a TMT bitstream (magic {bytes(magic)!r})")
+    if version != IMAGE_VERSION:
+        raise ValueError(f"container version {version}, this reader knows version {IMAGE_VERSION}")
+    if n % 4:
+        raise ValueError(f"{n} bytes: not a whole number of 32-bit words")
+    L = _check_geometry(S, K, patch)
+    ll, zl = nib & 15, nib >> 4
+    if ll > MAX_LANE_LOG2 or zl > MAX_LANE_LOG2:
+        raise ValueError(f"lane fields 2^{ll} / 2^{zl}: at most 2^{MAX_LANE_LOG2} lanes")
+    if O > S // 2:
+        raise ValueError(f"overlap {O} above half the tile size {S}")
+    if width == 0 or height == 0:
+        raise ValueError(f"image size {width}x{height}: width and height must be >= 1")
+    if chunk == 0:
+        raise ValueError("chunk 0: the encoder's tile batch must be >= 1")
+    if zero:
+        raise ValueError(f"reserved bytes 18-19 hold {zero:#06x}, must be zero")
+    if T > MAX_TILES:
+        raise ValueError(f"{T} tiles: at most {MAX_TILES}")
+    g = grid(height, width, S, O)
+    if T != g.T:
+        raise ValueError(f"{T} tiles, but {width}x{height} at tile size {S}, overlap {O} has {g.ny} x {g.nx} = {g.T}")
+    body0 = IMAGE_HEADER_BYTES + 8 * T
+    if n < body0:
+        raise ValueError(f"{n} bytes: the header and the table of {T} tiles take {body0}")
+    table = np.frombuffer(mv, dtype="<u4", count=2 * T, offset=IMAGE_HEADER_BYTES).reshape(T, 2)
+    for t in range(T):
+        if table[t, 0] < 2 or table[t, 1] < 2:
+            raise ValueError(f"tile {t}: z record of {table[t, 0]} and y record of {table[t, 1]} words, each holds at "
+                             f"least 2")
+    W = id_words(L, K)
+    need = body0 + 4 * (T * W + int(table.sum(dtype=np.int64)))
+    if n != need:
+        raise ValueError(f"{n} bytes: the header, the table and the {T} tiles it lists take {need}")
+    ids, zs, ys, at = [], [], [], body0
+    for t in range(T):
+        ids.append(np.frombuffer(mv, dtype="<u4", count=W, offset=at))
+        z0 = at + 4 * W
+        y0 = z0 + 4 * int(table[t, 0])
+        at = y0 + 4 * int(table[t, 1])
+        zs.append(mv[z0:y0])
+        ys.append(mv[y0:at])
+    return ImageBlob(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids, zs, ys)
+
+
+def tile_blob(parsed: ImageBlob, t: int) -> bytes:
+    """the version-1 TMC blob of tile t of a parsed TMT file (no original size): what MCM.encode_bytes gives for
+    that tile, and what parse() / MCM.decode_bytes read"""
+    p = parsed
+    if not 0 <= t < p.num_tiles:
+        raise ValueError(f"tile {t} outside 0..{p.num_tiles - 1}")
+    return assemble(p.img_size, p.num_keep_patches, p.patch_size, p.lanes, p.z_lanes, None, p.ids[t], p.z[t], p.y[t])
 
 
 def pack_ids_host(ids_keep, L: int) -> np.ndarray:

@@ -2,6 +2,10 @@
 
     python -m textmae_amd.codec encode -c CKPT -d FOLDER -o OUT [--lanes N --batch B]
     python -m textmae_amd.codec decode -c CKPT -d OUT -o PNGS [--original_size]
+    python -m textmae_amd.codec encode --tiled [--overlap N] -c CKPT -d FOLDER -o OUT
+
+``encode --tiled`` codes every image at its own resolution as overlapping model-sized tiles (MCM.encode_image,
+one ``<name>.tmt`` each); ``decode`` takes ``.tmt`` files next to ``.tmc`` ones and saves them at their native size.
 
 ``encode`` reads FOLDER through ``data.ImageFolderLoader`` (the test transform: bicubic resize to the model's
 size, scores from ``<FOLDER>_scores/test.pt`` or the device producer) and writes one ``<name>.tmc`` per image,
@@ -17,9 +21,11 @@ from pathlib import Path
 
 import torch
 
+from PIL import Image
+
 from . import bitstream
 from .data import ImageFolderLoader
-from .testing import load_checkpoint, save_output
+from .testing import collect_images, load_checkpoint, save_output
 
 
 def _model(checkpoint, num_keep_patches, input_size, half):
@@ -31,8 +37,33 @@ def _model(checkpoint, num_keep_patches, input_size, half):
 
 
 @torch.no_grad()
+def encode_tiled(args, model):
+    """--tiled: every image at its own resolution (no resize, no loader) -> <name>.tmt, MCM.encode_image"""
+    import numpy as np
+
+    files = collect_images(args.dataset)
+    if not files:
+        print(f"Error: no images found in {args.dataset}.", file=sys.stderr)
+        sys.exit(1)
+    os.makedirs(args.output, exist_ok=True)
+    nbytes = npixels = 0
+    for p in files:
+        a = np.array(Image.open(p).convert("RGB"))
+        blob = model.encode_image(a, overlap=args.overlap, lanes=args.lanes, tile_batch=args.batch)
+        with open(os.path.join(args.output, p.stem + ".tmt"), "wb") as f:
+            f.write(blob)
+        nbytes += len(blob)
+        npixels += a.shape[0] * a.shape[1]
+    print(f"{len(files)} images -> {args.output}: {nbytes} bytes, {8.0 * nbytes / npixels:.4f} bpp over "
+          f"{npixels} pixels at the images' own sizes")
+    return len(files)
+
+
+@torch.no_grad()
 def encode(args):
     model = _model(args.checkpoint, args.num_keep_patches, args.input_size, args.half)
+    if args.tiled:
+        return encode_tiled(args, model)
     loader = ImageFolderLoader(args.dataset, "test", args.batch, size=args.input_size,
                                patch=model.encoder_embed.patch_size[0])
     os.makedirs(args.output, exist_ok=True)
@@ -52,13 +83,21 @@ def encode(args):
 @torch.no_grad()
 def decode(args):
     files = sorted(Path(args.dataset).glob("*.tmc"))
-    if not files:
-        print(f"Error: no .tmc files found in {args.dataset}.", file=sys.stderr)
+    tiled = sorted(Path(args.dataset).glob("*.tmt"))
+    if not files and not tiled:
+        print(f"Error: no .tmc or .tmt files found in {args.dataset}.", file=sys.stderr)
         sys.exit(1)
-    with open(files[0], "rb") as f:
-        head = bitstream.parse(f.read())
+    first = min(files[:1] + tiled[:1])
+    with open(first, "rb") as f:
+        head = (bitstream.parse_image if first.suffix == ".tmt" else bitstream.parse)(f.read())
     model = _model(args.checkpoint, head.num_keep_patches, head.img_size, args.half)
     os.makedirs(args.output, exist_ok=True)
+    for p in tiled:  # one image each, at its own size
+        try:
+            a = model.decode_image(p.read_bytes(), out="u8")
+        except ValueError as e:
+            raise ValueError(f"{p.name}: {e}") from None
+        Image.fromarray(a.cpu().numpy()).save(os.path.join(args.output, p.stem + ".png"))
     for s in range(0, len(files), args.batch):
         group = files[s:s + args.batch]
         blobs = [p.read_bytes() for p in group]
@@ -69,8 +108,8 @@ def decode(args):
         for b, p in enumerate(group):
             size = out["orig_sizes"][b]
             save_output(out["x_hat"][b], size, p.stem + ".png", args.output, args.original_size and size is not None)
-    print(f"{len(files)} images -> {args.output}")
-    return len(files)
+    print(f"{len(files) + len(tiled)} images -> {args.output}")
+    return len(files) + len(tiled)
 
 
 def setup_args():
@@ -88,6 +127,10 @@ def setup_args():
     q.add_argument("--lanes", type=int, default=1, choices=[1, 2, 4, 8, 16, 32, 64], help="interleaved y lanes")
     q.add_argument("--num_keep_patches", type=int, default=144)
     q.add_argument("--input_size", type=int, default=224)
+    q.add_argument("--tiled", action="store_true",
+                   help="code every image at its own resolution as overlapping model-sized tiles -> <name>.tmt "
+                        "(--batch tiles per device call)")
+    q.add_argument("--overlap", type=int, default=32, help="tile overlap in pixels (--tiled), 0..input_size / 2")
     sub.choices["decode"].add_argument("--original_size", action="store_true",
                                        help="save each output resized to the size its file recorded")
     return p

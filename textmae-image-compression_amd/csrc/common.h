@@ -189,6 +189,13 @@ __device__ __forceinline__ uint4 pack8_bf16(f32x4 a, f32x4 b) {
   return *reinterpret_cast<uint4*>(&o);
 }
 
+// scores.imread_gray for non-JPEG files (libpng's 15-bit rgb_to_gray, OpenCV's PNG decoder path):
+//   gray = (9798 R + 19235 G + 3735 B + 16384) >> 15
+// shared by tmae_rgb_to_gray_u8 (resize.hip) and tmae_tile_cut_u8 (tile.hip)
+__device__ __forceinline__ unsigned int rgb_gray15(unsigned int r, unsigned int g, unsigned int b) {
+  return (9798u * r + 19235u * g + 3735u * b + 16384u) >> 15;
+}
+
 // XCD-aware bijective block remap (cdna_hip_programming.md §5 "XCD swizzle must be bijective"):
 // blocks b and b+8 land on one XCD; give each XCD a contiguous run of logical tiles.
 // Sum over the 64 lanes of a wave, every lane getting the total, without the LDS crossbar: DPP quad permutes

@@ -223,11 +223,7 @@ extern "C" int tmae_resize_u8(const unsigned char* src, int n, int H, int W, int
 }
 
 // ---------------------------------------------------------------------------------------------- RGB -> gray
-// scores.imread_gray for non-JPEG files (libpng's 15-bit rgb_to_gray, OpenCV's PNG decoder path):
-//   gray = (9798 R + 19235 G + 3735 B + 16384) >> 15
-__device__ __forceinline__ unsigned int rs_gray(unsigned int r, unsigned int g, unsigned int b) {
-  return (9798u * r + 19235u * g + 3735u * b + 16384u) >> 15;
-}
+// scores.imread_gray for non-JPEG files: gray = rgb_gray15 (common.h)
 
 // four pixels per thread: three aligned dwords in, one out (both pointers 4-byte aligned)
 __global__ void __launch_bounds__(RS_THREADS)
@@ -235,10 +231,10 @@ rgb_to_gray4_kernel(const unsigned int* __restrict__ rgb, long long ngroups, uns
   const long long i = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
   if (i >= ngroups) return;
   const unsigned int w0 = rgb[3 * i], w1 = rgb[3 * i + 1], w2 = rgb[3 * i + 2];
-  const unsigned int g0 = rs_gray(w0 & 255, (w0 >> 8) & 255, (w0 >> 16) & 255);
-  const unsigned int g1 = rs_gray(w0 >> 24, w1 & 255, (w1 >> 8) & 255);
-  const unsigned int g2 = rs_gray((w1 >> 16) & 255, w1 >> 24, w2 & 255);
-  const unsigned int g3 = rs_gray((w2 >> 8) & 255, (w2 >> 16) & 255, w2 >> 24);
+  const unsigned int g0 = rgb_gray15(w0 & 255, (w0 >> 8) & 255, (w0 >> 16) & 255);
+  const unsigned int g1 = rgb_gray15(w0 >> 24, w1 & 255, (w1 >> 8) & 255);
+  const unsigned int g2 = rgb_gray15((w1 >> 16) & 255, w1 >> 24, w2 & 255);
+  const unsigned int g3 = rgb_gray15((w2 >> 8) & 255, (w2 >> 16) & 255, w2 >> 24);
   gray[i] = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
 }
 
@@ -247,7 +243,7 @@ rgb_to_gray_kernel(const unsigned char* __restrict__ rgb, long long first, long 
                    unsigned char* __restrict__ gray) {
   const long long i = first + (long long)blockIdx.x * RS_THREADS + threadIdx.x;
   if (i >= npixels) return;
-  gray[i] = (unsigned char)rs_gray(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+  gray[i] = (unsigned char)rgb_gray15(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
 }
 
 extern "C" int tmae_rgb_to_gray_u8(const unsigned char* rgb, long long npixels, unsigned char* gray, void* stream) {

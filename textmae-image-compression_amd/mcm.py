@@ -411,13 +411,36 @@ class MCM(CompressionModel):
         B = imgs.shape[0]
         if orig_sizes is not None and len(orig_sizes) != B:
             raise ValueError(f"{len(orig_sizes)} original sizes for {B} images")
-        out = self.compress_batch(imgs, total_scores, lanes, z_lanes)
-        lanes, z_lanes = out.get("lanes", (1, 1))
+        lanes, z_lanes, ids, z, y = self._encode_sections(imgs, total_scores, lanes, z_lanes)
         img, patch, K, _ = self._geometry()
-        ids = ops.ids_pack(self._exec.last_ids_shuffle, K).cpu().numpy()  # the one extra copy: B * W words
-        y, z = out["string"]
         return [bitstream.assemble(img, K, patch, lanes, z_lanes, None if orig_sizes is None else orig_sizes[b],
                                    ids[b], z[b], y[b]) for b in range(B)]
+
+    def _encode_sections(self, imgs, total_scores, lanes, z_lanes):
+        """the sections of encode_bytes' blobs (and of encode_image's tiles) -> (lanes, z_lanes, id words uint32-
+        compatible numpy [B, W], z records, y records): compress_batch, then the kept ids packed on the device"""
+        out = self.compress_batch(imgs, total_scores, lanes, z_lanes)
+        lanes, z_lanes = out.get("lanes", (1, 1))
+        ids = ops.ids_pack(self._exec.last_ids_shuffle, self._geometry()[2]).cpu().numpy()  # the one extra copy
+        y, z = out["string"]
+        return lanes, z_lanes, ids, z, y
+
+    def _decode_sections(self, ids, z, y, lanes, z_lanes, who):
+        """inverse of _encode_sections -> x_hat [B, 3, S, S]: the id words (B uint32 [W] rows) go up, ops.ids_unpack
+        validates and completes them on the device, the records take the decompress_batch path and the ids status
+        words are read with the coder's.  who: the calling method's name for the error message"""
+        _, _, K, L = self._geometry()
+        self.entropy_bottleneck._check_cdf()
+        self.gaussian_conditional._check_cdf()
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise ValueError(f"MCM.{who} runs on the MI355X kernels: move the model to the GPU")
+        strings = [[bytes(s) for s in y], [bytes(s) for s in z]]
+        words = torch.from_numpy(np.stack(ids).view(np.int32)).to(dev)
+        with torch.no_grad():
+            ex = self._executor(len(ids), dev)
+            _, rest, status = ops.ids_unpack(words, L, K)
+            return ex.decompress_batch(strings, torch.Size([ex.hz, ex.hz]), rest, lanes, z_lanes, ids_status=status)
 
     def decode_bytes(self, blobs):
         """inverse of encode_bytes -> {"x_hat": [B, 3, S, S], "orig_sizes": [(width, height) or None per image]}.
@@ -446,19 +469,82 @@ class MCM(CompressionModel):
                 raise ValueError(f"blob {i}: lanes ({p.lanes}, {p.z_lanes}) differ from blob 0's "
                                  f"({parsed[0].lanes}, {parsed[0].z_lanes}): decode them in separate calls")
             parsed.append(p)
-        self.entropy_bottleneck._check_cdf()
-        self.gaussian_conditional._check_cdf()
+        x_hat = self._decode_sections([p.ids for p in parsed], [p.z for p in parsed], [p.y for p in parsed],
+                                      parsed[0].lanes, parsed[0].z_lanes, "decode_bytes")
+        return {"x_hat": x_hat, "orig_sizes": [p.orig_size for p in parsed]}
+
+    def encode_image(self, rgb_u8, overlap=32, lanes=1, z_lanes=None, tile_batch=16):
+        """an image at its own resolution -> one TMT file (bitstream.assemble_image).  rgb_u8: uint8
+        [H, W, 3], numpy or tensor (a host image is uploaded once).  The image is cut into overlapping model-sized
+        tiles (tiling.py; overlap 0..img_size // 2) and every chunk of tile_batch tiles (the last may be smaller)
+        goes through ops.tile_cut_u8, scores.image_scores of the tiles' gray and the encode_bytes path, a batch of
+        tiles being a batch of images; a tile's bytes in the file are the id / z / y sections of its encode_bytes
+        blob.  Same preconditions and ValueErrors as compress_batch."""
+        from . import bitstream, tiling
+        from .coder import check_lanes
+        from .scores import image_scores
+
+        x = torch.from_numpy(np.ascontiguousarray(rgb_u8)) if isinstance(rgb_u8, np.ndarray) else rgb_u8
+        if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != 3:
+            what = f"{tuple(x.shape)} {x.dtype}" if torch.is_tensor(x) else type(rgb_u8).__name__
+            raise ValueError(f"encode_image: the image must be uint8 [H, W, 3], got {what}")
+        img, patch, K, _ = self._geometry()
+        H, W = int(x.shape[0]), int(x.shape[1])
+        if H >= 1 << 16 or W >= 1 << 16:
+            raise ValueError(f"encode_image: {W}x{H} pixels do not fit the file's u16 size fields")
+        g = tiling.grid(H, W, img, overlap)
+        tile_batch = int(tile_batch)
+        if not 1 <= tile_batch < 1 << 16:
+            raise ValueError(f"encode_image: tile_batch {tile_batch} outside 1..65535")
+        lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
         dev = next(self.parameters()).device
         if dev.type != "cuda":
-            raise ValueError("MCM.decode_bytes runs on the MI355X kernels: move the model to the GPU")
-        strings = [[bytes(p.y) for p in parsed], [bytes(p.z) for p in parsed]]
-        words = torch.from_numpy(np.stack([p.ids for p in parsed]).view(np.int32)).to(dev)
-        with torch.no_grad():
-            ex = self._executor(len(parsed), dev)
-            _, rest, status = ops.ids_unpack(words, L, K)
-            x_hat = ex.decompress_batch(strings, torch.Size([ex.hz, ex.hz]), rest, parsed[0].lanes,
-                                        parsed[0].z_lanes, ids_status=status)
-        return {"x_hat": x_hat, "orig_sizes": [p.orig_size for p in parsed]}
+            raise ValueError("MCM.encode_image runs on the MI355X kernels: move the model to the GPU")
+        x = x.to(dev).contiguous()
+        ids, zs, ys = [], [], []
+        for t0 in range(0, g.T, tile_batch):
+            tiles, gray = ops.tile_cut_u8(x, img, g.O, t0, min(tile_batch, g.T - t0))
+            _, _, i, z, y = self._encode_sections(tiles, image_scores(gray, img, patch), lanes, z_lanes)
+            ids.append(i)
+            zs += list(z)
+            ys += list(y)
+        return bitstream.assemble_image(img, K, patch, lanes, z_lanes, g.O, W, H, tile_batch, np.concatenate(ids),
+                                        zs, ys)
+
+    def decode_image(self, blob, tile_batch=None, out="f32"):
+        """inverse of encode_image -> f32 [3, H, W] (out="f32") or uint8 [H, W, 3] (out="u8", the f32 image through
+        clamp(0, 1).mul(255).round()).  The file is parsed on the host first (bitstream.parse_image): a malformed
+        one, or one of another geometry than this model's, raises ValueError before anything is launched.  The tiles
+        are decoded in chunks of tile_batch (None: the file's chunk, the encoder's batching) through the
+        decode_bytes path into one [T, 3, S, S] buffer, which one ops.tile_blend turns into the image.  A corrupt
+        tile raises ValueError naming its index in the file."""
+        import re
+
+        from . import bitstream
+
+        if out not in ("f32", "u8"):
+            raise ValueError(f"decode_image: out must be 'f32' or 'u8', got {out!r}")
+        p = bitstream.parse_image(blob)
+        img, patch, K, _ = self._geometry()
+        if (p.img_size, p.patch_size, p.num_keep_patches) != (img, patch, K):
+            raise ValueError(f"coded for img_size {p.img_size}, patch_size {p.patch_size}, "
+                             f"num_keep_patches {p.num_keep_patches}; this model has {img}, {patch}, {K}")
+        n = p.chunk if tile_batch is None else int(tile_batch)
+        if n < 1:
+            raise ValueError(f"decode_image: tile_batch {n} must be >= 1")
+        T, tiles = p.num_tiles, None
+        for t0 in range(0, T, n):
+            t1 = min(t0 + n, T)
+            try:
+                x_hat = self._decode_sections(p.ids[t0:t1], p.z[t0:t1], p.y[t0:t1], p.lanes, p.z_lanes,
+                                              "decode_image")
+            except ValueError as e:  # the batch path names the image of its call: that is tile t0 + b of the file
+                raise ValueError(re.sub(r"\bimage (\d+)", lambda m: f"tile {t0 + int(m.group(1))}", str(e), count=1)
+                                 ) from None
+            if tiles is None:
+                tiles = torch.empty((T,) + tuple(x_hat.shape[1:]), dtype=torch.float32, device=x_hat.device)
+            tiles[t0:t1].copy_(x_hat)
+        return ops.tile_blend(tiles, p.height, p.width, p.overlap, out=out)
 
 
 class _LazyStreams(collections.abc.Mapping):

@@ -22,7 +22,7 @@ __all__ = [
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "rans_encode_lanes", "rans_decode_lanes", "ids_pack", "ids_unpack",
-    "resize_tables", "resize_u8", "rgb_to_gray_u8",
+    "resize_tables", "resize_u8", "rgb_to_gray_u8", "tile_cut_u8", "tile_blend",
     "mae_loss", "TMAE_F32", "TMAE_BF16", "ACT_NONE", "ACT_GELU",
 ]
 
@@ -908,3 +908,63 @@ def rgb_to_gray_u8(src):
     with torch.cuda.device(s.device):
         _lib.call("tmae_rgb_to_gray_u8", s.data_ptr(), out.numel(), out.data_ptr(), _stream())
     return out
+
+
+# --------------------------------------------------------------------------------------- tiled images
+def tile_cut_u8(src, S: int, O: int, t0: int = 0, nt=None, tiles=None, gray=None):
+    """tiles t0 .. t0 + nt (nt=None: to the last) of the overlapping S x S tile grid of an image (tiling.py,
+    csrc/tile.hip): src uint8 [H, W, 3] on the device -> (tiles f32 [nt, 3, S, S] = v / 255, the test transform's
+    ToTensor bit for bit, gray uint8 [nt, S, S] = rgb_to_gray_u8 of the tiles).  Samples outside the image are the
+    nearest edge pixel.  tiles= / gray= take preallocated outputs."""
+    from .tiling import grid
+
+    if src.dim() != 3 or src.shape[2] != 3:
+        raise ValueError(f"tile_cut_u8: src must be uint8 [H, W, 3], got {tuple(src.shape)}")
+    s = _need(src, torch.uint8, "src")
+    H, W = int(s.shape[0]), int(s.shape[1])
+    g = grid(H, W, S, O)
+    t0 = int(t0)
+    nt = g.T - t0 if nt is None else int(nt)
+    if t0 < 0 or nt < 1 or t0 + nt > g.T:
+        raise ValueError(f"tile_cut_u8: tiles {t0}..{t0 + nt} outside the image's {g.T} ({g.ny} x {g.nx})")
+    if tiles is None:
+        tiles = torch.empty((nt, 3, g.S, g.S), dtype=torch.float32, device=s.device)
+    elif tuple(_need(tiles, torch.float32, "tiles").shape) != (nt, 3, g.S, g.S):
+        raise ValueError(f"tile_cut_u8: tiles must be [{nt}, 3, {g.S}, {g.S}], got {tuple(tiles.shape)}")
+    if gray is None:
+        gray = torch.empty((nt, g.S, g.S), dtype=torch.uint8, device=s.device)
+    elif tuple(_need(gray, torch.uint8, "gray").shape) != (nt, g.S, g.S):
+        raise ValueError(f"tile_cut_u8: gray must be [{nt}, {g.S}, {g.S}], got {tuple(gray.shape)}")
+    with torch.cuda.device(s.device):
+        _lib.call("tmae_tile_cut_u8", s.data_ptr(), H, W, g.S, g.O, t0, nt, tiles.data_ptr(), gray.data_ptr(),
+                  _stream())
+    return tiles, gray
+
+
+def tile_blend(tiles, H: int, W: int, O: int, out="f32", out_f32=None, out_u8=None):
+    """inverse of tile_cut_u8 on decoded tiles: tiles f32 [T, 3, S, S] (all tiles of the H x W image) -> the
+    weighted blend, out="f32": f32 [3, H, W]; "u8": uint8 [H, W, 3] = clamp(0, 1).mul(255).round() of it; "both":
+    the pair, from one launch.  out_f32= / out_u8= take preallocated outputs."""
+    from .tiling import grid
+
+    if out not in ("f32", "u8", "both"):
+        raise ValueError(f"tile_blend: out must be 'f32', 'u8' or 'both', got {out!r}")
+    t = _need(tiles, torch.float32, "tiles")
+    if t.dim() != 4 or t.shape[1] != 3 or t.shape[2] != t.shape[3]:
+        raise ValueError(f"tile_blend: tiles must be f32 [T, 3, S, S], got {tuple(t.shape)}")
+    g = grid(H, W, int(t.shape[2]), O)
+    if t.shape[0] != g.T:
+        raise ValueError(f"tile_blend: {t.shape[0]} tiles, but {g.H}x{g.W} at tile size {g.S}, overlap {g.O} has "
+                         f"{g.ny} x {g.nx} = {g.T}")
+    f32 = u8 = None
+    if out in ("f32", "both"):
+        f32 = out_f32 if out_f32 is not None else torch.empty((3, g.H, g.W), dtype=torch.float32, device=t.device)
+        if tuple(_need(f32, torch.float32, "out_f32").shape) != (3, g.H, g.W):
+            raise ValueError(f"tile_blend: out_f32 must be [3, {g.H}, {g.W}], got {tuple(f32.shape)}")
+    if out in ("u8", "both"):
+        u8 = out_u8 if out_u8 is not None else torch.empty((g.H, g.W, 3), dtype=torch.uint8, device=t.device)
+        if tuple(_need(u8, torch.uint8, "out_u8").shape) != (g.H, g.W, 3):
+            raise ValueError(f"tile_blend: out_u8 must be [{g.H}, {g.W}, 3], got {tuple(u8.shape)}")
+    with torch.cuda.device(t.device):
+        _lib.call("tmae_tile_blend", t.data_ptr(), g.H, g.W, g.S, g.O, _p(f32), _p(u8), _stream())
+    return (f32, u8) if out == "both" else (f32 if out == "f32" else u8)

@@ -13,6 +13,10 @@ Same function names and arithmetic as the reference (testing.py:40-165, 199-250)
 ``--bitstream DIR`` (no reference counterpart) sends every image through a self-contained file ``DIR/<name>.tmc``
 (MCM.encode_bytes, written, read back, MCM.decode_bytes) and reports the files' own bpp, 8 * size / pixels, which
 counts the container header and the side information in full.
+``--tiled [--overlap N]`` (no reference counterpart) codes every image at its own resolution as overlapping
+model-sized tiles (MCM.encode_image / decode_image; with ``--bitstream DIR`` through
+``DIR/<name>.tmt``): PSNR / MS-SSIM against the original pixels, bpp = 8 * file size / (W * H); an image whose
+smaller side is at most 160 is too small for MS-SSIM's five scales and reports PSNR only.
 Deviation: ``inference_entropy_estimation`` takes the scores (the reference calls model.forward(x) without
 them, testing.py:106, which raises).
 """
@@ -139,6 +143,67 @@ def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_d
             "encoding_time": enc_time, "decoding_time": dec_time}
 
 
+MS_SSIM_MIN_SIDE = 161  # five scales of an 11-tap window: the smaller side must exceed 160 (tmae_image_metrics)
+
+
+@torch.no_grad()
+def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, output_dir=None, lanes=None, tile_batch=16):
+    """--tiled: the image at its own resolution, rgb uint8 [H, W, 3] -> MCM.encode_image -> (with bitstream_dir)
+    DIR/<name>.tmt, read back -> MCM.decode_image.  PSNR / MS-SSIM against the original pixels at that resolution,
+    bpp = 8 * file size / (W * H).  An image too small for MS-SSIM's five scales gets PSNR only (no "ms-ssim")."""
+    import math
+
+    device = next(model.parameters()).device
+    x = torch.from_numpy(np.ascontiguousarray(rgb)).to(device)
+    H, W = int(x.shape[0]), int(x.shape[1])
+    torch.cuda.synchronize()
+    start = time.time()
+    blob = model.encode_image(x, overlap=overlap, lanes=1 if lanes is None else lanes, tile_batch=tile_batch)
+    enc_time = time.time() - start
+    if bitstream_dir is not None:
+        path = os.path.join(bitstream_dir, Path(file_name).stem + ".tmt")
+        with open(path, "wb") as f:
+            f.write(blob)
+        with open(path, "rb") as f:
+            blob = f.read()
+    start = time.time()
+    rec = model.decode_image(blob)
+    torch.cuda.synchronize()
+    dec_time = time.time() - start
+    org = x.permute(2, 0, 1).float().div(255).unsqueeze(0)
+    rv = {"bpp": 8.0 * len(blob) / (W * H), "encoding_time": enc_time, "decoding_time": dec_time}
+    if min(H, W) >= MS_SSIM_MIN_SIDE:
+        rv.update(compute_metrics(org, rec.unsqueeze(0), 255))
+    else:  # compute_metrics' PSNR alone: both images rounded to 0..255
+        q = rec.mul(255).clamp(0, 255).round()
+        mse = float((org[0].mul(255).round() - q).square().mean())
+        rv["psnr"] = 20.0 * math.log10(255.0) - 10.0 * math.log10(mse) if mse > 0 else float("inf")
+    if output_dir is not None:
+        from PIL import Image
+
+        a = rec.clamp(0, 1).mul(255).round().byte().permute(1, 2, 0)  # save_output's chain, at the image's own size
+        Image.fromarray(a.cpu().numpy()).save(os.path.join(output_dir, Path(file_name).stem + ".png"))
+    return rv
+
+
+def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_dir=None, tile_batch=16):
+    """--tiled counterpart of eval_model over image files: every metric averaged over the images that have it
+    -> (metrics, number of images with MS-SSIM)"""
+    from PIL import Image
+
+    for d in (output_dir, bitstream_dir):
+        if d is not None:
+            os.makedirs(d, exist_ok=True)
+    sums, counts = defaultdict(float), defaultdict(int)
+    for p in filepaths:
+        rv = inference_tiled(model, np.array(Image.open(p).convert("RGB")), p.name, overlap, bitstream_dir, output_dir,
+                             lanes, tile_batch)
+        for k, v in rv.items():
+            sums[k] += v
+            counts[k] += 1
+    return {k: sums[k] / counts[k] for k in sums}, counts["ms-ssim"]
+
+
 @torch.no_grad()
 def inference_entropy_estimation(model, x, total_score):
     """testing.py:103-120 with the scores passed (the reference omits them and raises)"""
@@ -236,6 +301,11 @@ def setup_args():
     p.add_argument("--bitstream", type=str, default=None, metavar="DIR",
                    help="code every image into the self-contained file DIR/<name>.tmc (encode_bytes, --lanes y lanes, "
                         "default 1), read it back and decode that (decode_bytes); bpp = 8 * file size / pixels")
+    p.add_argument("--tiled", action="store_true",
+                   help="code every image at its own resolution as overlapping model-sized tiles (encode_image / "
+                        "decode_image; with --bitstream DIR through DIR/<name>.tmt); metrics against the original "
+                        "pixels, bpp = 8 * file size / (W * H)")
+    p.add_argument("--overlap", type=int, default=32, help="tile overlap in pixels (--tiled)")
     return p
 
 
@@ -245,27 +315,41 @@ def main(argv):
     if not filepaths:
         print("Error: no images found in directory.", file=sys.stderr)
         sys.exit(1)
-    ds = Path(args.dataset)
-    score_file = ds.parent / f"{ds.name}_scores" / "test.pt"
-    if score_file.exists():
-        scores = torch.load(score_file, map_location="cpu", weights_only=True)
-    else:
-        from .scores import preprocess_image_scores
+    if args.tiled and args.entropy_estimation:
+        print("Error: --tiled codes real files; it does not combine with --entropy-estimation.", file=sys.stderr)
+        sys.exit(1)
+    if not args.tiled:
+        ds = Path(args.dataset)
+        score_file = ds.parent / f"{ds.name}_scores" / "test.pt"
+        if score_file.exists():
+            scores = torch.load(score_file, map_location="cpu", weights_only=True)
+        else:
+            from .scores import preprocess_image_scores
 
-        scores = preprocess_image_scores(filepaths, args.input_size)
-    images = load_test_images(filepaths, args.input_size)
+            scores = preprocess_image_scores(filepaths, args.input_size)
+        images = load_test_images(filepaths, args.input_size)
     results = defaultdict(list)
+    with_msssim = 0
     for run in args.checkpoint_paths:
         model = load_checkpoint(args.num_keep_patches, run, args.input_size).to("cuda")
         if args.half:
             model.compute_dtype = torch.bfloat16
         model.update(force=True)
-        m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths], args.entropy_estimation,
-                       lanes=args.lanes, original_size=args.original_size, bitstream_dir=args.bitstream)
+        if args.tiled:
+            m, with_msssim = eval_tiled(model, args.output_path, filepaths, args.overlap, lanes=args.lanes,
+                                        bitstream_dir=args.bitstream)
+        else:
+            m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths],
+                           args.entropy_estimation, lanes=args.lanes, original_size=args.original_size,
+                           bitstream_dir=args.bitstream)
         for k, v in m.items():
             results[k].append(v)
     desc = "entropy estimation" if args.entropy_estimation else args.entropy_coder
-    if args.bitstream is not None and not args.entropy_estimation:
+    if args.tiled:
+        desc += (f"; tiled at the images' own resolution, overlap {args.overlap}: bpp of the .tmt files over W x H; "
+                 f"MS-SSIM over the {with_msssim} of {len(filepaths)} images whose smaller side exceeds "
+                 f"{MS_SSIM_MIN_SIDE - 1}, PSNR only for the others")
+    elif args.bitstream is not None and not args.entropy_estimation:
         desc += "; bpp of the .tmc files: header and side information counted in full"
     output = {"name": "MCM", "description": f"Inference ({desc})", "results": results}
     print(json.dumps(output, indent=2))

@@ -489,6 +489,16 @@ int tmae_tile_cut_u8(const unsigned char* src, int H, int W, int S, int O, int t
  * out_u8 = round-half-even(clamp(v, 0, 1) * 255). */
 int tmae_tile_blend(const float* tiles, int H, int W, int S, int O, float* out_f32, unsigned char* out_u8,
                     void* stream);
+/* region decode: R windows of h x w pixels, each of its own image, blended from a compact buffer
+ * tiles f32 [N][3][S][S] that holds only the decoded tiles -> out_f32 [R][3][h][w] and / or out_u8 [R][h][w][3]
+ * (either may be NULL, not both).  map int32 [map_len]: one slot map per image, one after the other; entry
+ * map_base + t is the slot of tile t of that image in tiles (-1: not decoded).  desc int32 [R][8]: per window the
+ * image's H, W, the window origin y0, x0, the image's map_base, three unused words.  Pixel (i, j) of window r is
+ * pixel (y0 + i, x0 + j) of tmae_tile_blend of that image, bit for bit.  The caller guarantees that every tile a
+ * window needs has a slot; the kernel clamps coordinates, map indices and slots, so nothing is read outside map
+ * and tiles whatever the two arrays hold. */
+int tmae_tile_blend_crops(const float* tiles, int N, const int* map, long long map_len, const int* desc, int R,
+                          int h, int w, int S, int O, float* out_f32, unsigned char* out_u8, void* stream);
 
 /* ---------------------------------------------------------------- VGG16 feature loss (MCM.forward_loss,
  * models/Compression/loss/vgg.py:86-115 with common/image_utils.py:4-23).  The convolutions are tmae_conv3x3

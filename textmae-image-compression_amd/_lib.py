@@ -186,6 +186,7 @@ SIGNATURES = {
     # tiled full-resolution coding (csrc/tile.hip)
     "tmae_tile_cut_u8": [P, I, I, I, I, I, I, P, P, P],
     "tmae_tile_blend": [P, I, I, I, I, P, P, P],
+    "tmae_tile_blend_crops": [P, I, P, LL, P, I, I, I, I, I, P, P, P],
     # VGG16 feature loss glue
     "tmae_vgg_prep": [P, I, I, I, I, I, P, I, P],
     "tmae_vgg_prep_bwd": [P, I, I, I, I, I, P, I, P],

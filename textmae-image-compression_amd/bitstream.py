@@ -22,7 +22,9 @@ them as the oracle.  Nothing here touches the device.
 
 A second format, b"TMT" version 1 (``assemble_image`` / ``parse_image`` / ``tile_blob``, layout further down), holds
 one image coded at its own resolution as overlapping tiles: the sections of the tiles' TMC blobs behind one header
-and a table of record lengths (``MCM.encode_image`` / ``decode_image``).
+and a table of record lengths (``MCM.encode_image`` / ``decode_image``).  ``read_image_index`` /
+``read_tiles`` read such a file's header and table and then single tiles, from bytes or from a file object, without
+touching the other tiles (``MCM.decode_region`` / ``decode_crops``).
 """
 from __future__ import annotations
 
@@ -274,6 +276,124 @@ def parse_image(blob) -> ImageBlob:
         zs.append(mv[z0:y0])
         ys.append(mv[y0:at])
     return ImageBlob(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids, zs, ys)
+
+
+class ImageIndex(NamedTuple):
+    """read_image_index()'s result: the header fields of ImageBlob, then per tile the byte offsets of its sections in
+    the file (prefix sums of the table): tile t is bytes ids_at[t] .. end_at[t], its z record starts at z_at[t] and
+    its y record at y_at[t]"""
+    img_size: int
+    num_keep_patches: int
+    patch_size: int
+    lanes: int
+    z_lanes: int
+    overlap: int
+    width: int
+    height: int
+    chunk: int
+    ids_at: np.ndarray       # int64 [T] each
+    z_at: np.ndarray
+    y_at: np.ndarray
+    end_at: np.ndarray
+
+    @property
+    def num_tiles(self) -> int:
+        return len(self.ids_at)
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.end_at[-1])
+
+
+def _source(src):
+    """(length in bytes, read(offset, size) -> bytes-like) of a bytes-like object or a seekable binary file object;
+    a file is only ever read at the ranges asked for"""
+    if hasattr(src, "seek") and hasattr(src, "read"):
+        n = src.seek(0, 2)
+
+        def read(at, size):
+            src.seek(at)
+            b = src.read(size)
+            if len(b) != size:
+                raise ValueError(f"read {len(b)} of the {size} bytes at offset {at}: the file changed or is not in "
+                                 f"binary mode")
+            return b
+
+        return n, read
+    mv = memoryview(src).cast("B") if not isinstance(src, memoryview) else src.cast("B")
+    return len(mv), lambda at, size: mv[at:at + size]
+
+
+def read_image_index(src) -> ImageIndex:
+    """the header and the table of a TMT file without its tiles (region decode): src is a bytes-like
+    object or a seekable binary file object, of which only the 24 header bytes and the 8 * T table bytes are read
+    (the length comes from a seek to the end).  Accepts the files parse_image accepts, with its ValueErrors for
+    every malformed field."""
+    from .tiling import MAX_TILES, grid
+
+    n, read = _source(src)
+    if n < IMAGE_HEADER_BYTES:
+        raise ValueError(f"{n} bytes: shorter than the {IMAGE_HEADER_BYTES}-byte header")
+    magic, version, S, K, patch, nib, O, width, height, chunk, zero, T = _IMAGE_HEADER.unpack(
+        read(0, IMAGE_HEADER_BYTES))
+    if magic != IMAGE_MAGIC:
+        raise ValueError(f"not a TMT bitstream (magic {bytes(magic)!r})")
+    if version != IMAGE_VERSION:
+        raise ValueError(f"container version {version}, this reader knows version {IMAGE_VERSION}")
+    if n % 4:
+        raise ValueError(f"{n} bytes: not a whole number of 32-bit words")
+    L = _check_geometry(S, K, patch)
+    ll, zl = nib & 15, nib >> 4
+    if ll > MAX_LANE_LOG2 or zl > MAX_LANE_LOG2:
+        raise ValueError(f"lane fields 2^{ll} / 2^{zl}: at most 2^{MAX_LANE_LOG2} lanes")
+    if O > S // 2:
+        raise ValueError(f"overlap {O} above half the tile size {S}")
+    if width == 0 or height == 0:
+        raise ValueError(f"image size {width}x{height}: width and height must be >= 1")
+    if chunk == 0:
+        raise ValueError("chunk 0: the encoder's tile batch must be >= 1")
+    if zero:
+        raise ValueError(f"reserved bytes 18-19 hold {zero:#06x}, must be zero")
+    if T > MAX_TILES:
+        raise ValueError(f"{T} tiles: at most {MAX_TILES}")
+    g = grid(height, width, S, O)
+    if T != g.T:
+        raise ValueError(f"{T} tiles, but {width}x{height} at tile size {S}, overlap {O} has {g.ny} x {g.nx} = {g.T}")
+    body0 = IMAGE_HEADER_BYTES + 8 * T
+    if n < body0:
+        raise ValueError(f"{n} bytes: the header and the table of {T} tiles take {body0}")
+    table = np.frombuffer(read(IMAGE_HEADER_BYTES, 8 * T), dtype="<u4").reshape(T, 2).astype(np.int64)
+    for t in range(T):
+        if table[t, 0] < 2 or table[t, 1] < 2:
+            raise ValueError(f"tile {t}: z record of {table[t, 0]} and y record of {table[t, 1]} words, each holds at "
+                             f"least 2")
+    W = id_words(L, K)
+    end_at = body0 + 4 * np.cumsum(W + table.sum(axis=1))
+    if n != end_at[-1]:
+        raise ValueError(f"{n} bytes: the header, the table and the {T} tiles it lists take {end_at[-1]}")
+    ids_at = np.concatenate([[body0], end_at[:-1]])
+    z_at = ids_at + 4 * W
+    return ImageIndex(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids_at, z_at, z_at + 4 * table[:, 0],
+                      end_at)
+
+
+def read_tiles(src, index: ImageIndex, tiles):
+    """(ids, z, y) of the listed tiles of the file read_image_index(src) gave the index of: per tile the uint32 [W]
+    id words and the two records, as parse_image gives them.  Reads one byte range per tile and nothing else."""
+    n, read = _source(src)
+    if n != index.nbytes:
+        raise ValueError(f"{n} bytes, but the index is of a file of {index.nbytes}")
+    ids, zs, ys = [], [], []
+    for t in tiles:
+        t = int(t)
+        if not 0 <= t < index.num_tiles:
+            raise ValueError(f"tile {t} outside 0..{index.num_tiles - 1}")
+        at, z0, y0, end = (int(a[t]) for a in (index.ids_at, index.z_at, index.y_at, index.end_at))
+        body = memoryview(read(at, end - at))
+        ids.append(np.frombuffer(body, dtype="<u4", count=(z0 - at) // 4))
+        zs.append(body[z0 - at:y0 - at])
+        ys.append(body[y0 - at:])
+    return ids, zs, ys
 
 
 def tile_blob(parsed: ImageBlob, t: int) -> bytes:

@@ -3,9 +3,12 @@
     python -m textmae_amd.codec encode -c CKPT -d FOLDER -o OUT [--lanes N --batch B]
     python -m textmae_amd.codec decode -c CKPT -d OUT -o PNGS [--original_size]
     python -m textmae_amd.codec encode --tiled [--overlap N] -c CKPT -d FOLDER -o OUT
+    python -m textmae_amd.codec decode --region X,Y,W,H -c CKPT -d OUT -o PNGS
 
 ``encode --tiled`` codes every image at its own resolution as overlapping model-sized tiles (MCM.encode_image,
 one ``<name>.tmt`` each); ``decode`` takes ``.tmt`` files next to ``.tmc`` ones and saves them at their native size.
+``decode --region X,Y,W,H`` saves that window of every ``.tmt`` file instead, reading and decoding only the tiles
+the window needs (MCM.decode_region); ``.tmc`` files beside them decode as before.
 
 ``encode`` reads FOLDER through ``data.ImageFolderLoader`` (the test transform: bicubic resize to the model's
 size, scores from ``<FOLDER>_scores/test.pt`` or the device producer) and writes one ``<name>.tmc`` per image,
@@ -89,12 +92,16 @@ def decode(args):
         sys.exit(1)
     first = min(files[:1] + tiled[:1])
     with open(first, "rb") as f:
-        head = (bitstream.parse_image if first.suffix == ".tmt" else bitstream.parse)(f.read())
+        head = bitstream.read_image_index(f) if first.suffix == ".tmt" else bitstream.parse(f.read())
     model = _model(args.checkpoint, head.num_keep_patches, head.img_size, args.half)
     os.makedirs(args.output, exist_ok=True)
     for p in tiled:  # one image each, at its own size
         try:
-            a = model.decode_image(p.read_bytes(), out="u8")
+            if args.region is None:
+                a = model.decode_image(p.read_bytes(), out="u8")
+            else:  # the file object: only the header, the table and the needed tiles are read
+                with open(p, "rb") as f:
+                    a = model.decode_region(f, *args.region, out="u8")
         except ValueError as e:
             raise ValueError(f"{p.name}: {e}") from None
         Image.fromarray(a.cpu().numpy()).save(os.path.join(args.output, p.stem + ".png"))
@@ -110,6 +117,15 @@ def decode(args):
             save_output(out["x_hat"][b], size, p.stem + ".png", args.output, args.original_size and size is not None)
     print(f"{len(files) + len(tiled)} images -> {args.output}")
     return len(files) + len(tiled)
+
+
+def _region(text):
+    """--region X,Y,W,H -> (x0, y0, w, h)"""
+    try:
+        x0, y0, w, h = (int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not X,Y,W,H (four integers)") from None
+    return x0, y0, w, h
 
 
 def setup_args():
@@ -133,6 +149,9 @@ def setup_args():
     q.add_argument("--overlap", type=int, default=32, help="tile overlap in pixels (--tiled), 0..input_size / 2")
     sub.choices["decode"].add_argument("--original_size", action="store_true",
                                        help="save each output resized to the size its file recorded")
+    sub.choices["decode"].add_argument("--region", type=_region, default=None, metavar="X,Y,W,H",
+                                       help="of every .tmt file, decode and save only this window (origin X,Y, "
+                                            "size W x H), from the tiles it needs")
     return p
 
 

@@ -546,6 +546,105 @@ class MCM(CompressionModel):
             tiles[t0:t1].copy_(x_hat)
         return ops.tile_blend(tiles, p.height, p.width, p.overlap, out=out)
 
+    def decode_region(self, src, x0, y0, w, h, out="f32", tile_batch=None):
+        """the window [x0, x0 + w) x [y0, y0 + h) of decode_image's image, bit for bit, from the tiles that window
+        needs alone -> f32 [3, h, w] (out="f32") or uint8 [h, w, 3] ("u8").  src: the TMT file as
+        a bytes-like object or a seekable binary file object, of which only the header, the table and those tiles'
+        bytes are read (bitstream.read_image_index / read_tiles).  The tiles tiling.region_tiles names are decoded
+        in chunks of tile_batch (None: the file's chunk) through the decode_bytes path into a compact buffer and
+        blended by one ops.tile_blend_crops.  A malformed file, one of another geometry or a window that is not
+        inside the image raises ValueError before anything is launched; a corrupt tile among the needed ones raises
+        ValueError naming its index in the file, and one the window does not need is never read."""
+        return self._decode_windows([src], [(x0, y0)], (w, h), out, tile_batch, "decode_region")[0]
+
+    def decode_crops(self, srcs, origins, size, out="f32", tile_batch=16):
+        """R windows of one size = (w, h) from TMT files, windows r at origins[r] = (x0, y0) of srcs[r] -> f32
+        [R, 3, h, w] or uint8 [R, h, w, 3], each window decode_region's.  srcs may hold the same object several
+        times: per distinct source the union of the tiles its windows need is read and decoded once.  The tiles of
+        all sources are batched together in chunks of tile_batch (sources coded with other lanes in batches of
+        their own) and one ops.tile_blend_crops produces all windows.  ValueErrors as decode_region, naming the
+        source by its first position in srcs; the sources of one call must agree in their overlap."""
+        srcs, origins = list(srcs), list(origins)
+        if len(srcs) != len(origins):
+            raise ValueError(f"decode_crops: {len(srcs)} sources but {len(origins)} origins: one of each per window")
+        if not srcs:
+            raise ValueError("decode_crops: no windows")
+        return self._decode_windows(srcs, origins, size, out, tile_batch, "decode_crops")
+
+    def _decode_windows(self, srcs, origins, size, out, tile_batch, who):
+        """decode_region / decode_crops: index every distinct source, list the tiles its windows need, decode them
+        grouped by lanes into one compact [N, 3, S, S] buffer (slot = position in that order), blend all windows"""
+        import re
+
+        from . import bitstream, tiling
+
+        if out not in ("f32", "u8"):
+            raise ValueError(f"{who}: out must be 'f32' or 'u8', got {out!r}")
+        many = who == "decode_crops"
+        img, patch, K, _ = self._geometry()
+        n = None if tile_batch is None else int(tile_batch)
+        if n is not None and n < 1:
+            raise ValueError(f"{who}: tile_batch {n} must be >= 1")
+        # distinct sources by identity, in order of appearance; where: a source's first position in srcs
+        first, where, index, grids, need, windows = {}, [], [], [], [], []
+        for r, (src, (x0, y0)) in enumerate(zip(srcs, origins)):
+            k = first.get(id(src))
+            try:
+                if k is None:
+                    p = bitstream.read_image_index(src)
+                    if (p.img_size, p.patch_size, p.num_keep_patches) != (img, patch, K):
+                        raise ValueError(f"coded for img_size {p.img_size}, patch_size {p.patch_size}, "
+                                         f"num_keep_patches {p.num_keep_patches}; this model has {img}, {patch}, {K}")
+                    if index and p.overlap != index[0].overlap:
+                        raise ValueError(f"overlap {p.overlap} differs from source 0's {index[0].overlap}: decode "
+                                         f"them in separate calls")
+                    k = first[id(src)] = len(index)
+                    where.append(r)
+                    index.append(p)
+                    grids.append(tiling.grid(p.height, p.width, p.img_size, p.overlap))
+                    need.append(set())
+                need[k].update(tiling.region_tiles(grids[k], x0, y0, size[0], size[1]))
+            except ValueError as e:
+                raise ValueError(f"source {r}: {e}" if many else str(e)) from None
+            windows.append((k, int(x0), int(y0)))
+        # the jobs: (source, tile) in slot order, sources of equal lanes next to each other
+        jobs = []
+        for lanes in sorted({(p.lanes, p.z_lanes) for p in index}):
+            jobs += [(k, t) for k, p in enumerate(index) if (p.lanes, p.z_lanes) == lanes for t in sorted(need[k])]
+        slots = [[-1] * g.T for g in grids]
+        for s, (k, t) in enumerate(jobs):
+            slots[k][t] = s
+        sections = {}
+        for k, p in enumerate(index):
+            tiles_k = sorted(need[k])
+            for t, i, z, y in zip(tiles_k, *bitstream.read_tiles(srcs[where[k]], p, tiles_k)):
+                sections[k, t] = (i, z, y)
+        n = index[0].chunk if n is None else n
+        job_lanes = [(index[k].lanes, index[k].z_lanes) for k, _ in jobs]
+        tiles, s0 = None, 0
+        while s0 < len(jobs):  # chunks of at most n jobs of equal lanes
+            lanes = job_lanes[s0]
+            s1 = s0 + 1
+            while s1 < min(s0 + n, len(jobs)) and job_lanes[s1] == lanes:
+                s1 += 1
+            part = [sections[j] for j in jobs[s0:s1]]
+            try:
+                x_hat = self._decode_sections([a[0] for a in part], [a[1] for a in part], [a[2] for a in part],
+                                              lanes[0], lanes[1], who)
+            except ValueError as e:  # the batch path names the image of its call: that is job s0 + b
+
+                def name(m, s0=s0):
+                    k, t = jobs[s0 + int(m.group(1))]
+                    return f"tile {t} of source {where[k]}" if many else f"tile {t}"
+
+                raise ValueError(re.sub(r"\bimage (\d+)", name, str(e), count=1)) from None
+            if tiles is None:
+                tiles = torch.empty((len(jobs),) + tuple(x_hat.shape[1:]), dtype=torch.float32, device=x_hat.device)
+            tiles[s0:s1].copy_(x_hat)
+            s0 = s1
+        images = [(g.H, g.W, slots[k]) for k, g in enumerate(grids)]
+        return ops.tile_blend_crops(tiles, images, windows, size, index[0].overlap, out=out)
+
 
 class _LazyStreams(collections.abc.Mapping):
     """_Executor.last_streams of compress_batch: the keys compress sets, as host arrays copied from the device on

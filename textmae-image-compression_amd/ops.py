@@ -22,7 +22,7 @@ __all__ = [
     "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "rans_encode_lanes", "rans_decode_lanes", "ids_pack", "ids_unpack",
-    "resize_tables", "resize_u8", "rgb_to_gray_u8", "tile_cut_u8", "tile_blend",
+    "resize_tables", "resize_u8", "rgb_to_gray_u8", "tile_cut_u8", "tile_blend", "tile_blend_crops",
     "mae_loss", "TMAE_F32", "TMAE_BF16", "ACT_NONE", "ACT_GELU",
 ]
 
@@ -967,4 +967,72 @@ def tile_blend(tiles, H: int, W: int, O: int, out="f32", out_f32=None, out_u8=No
             raise ValueError(f"tile_blend: out_u8 must be [{g.H}, {g.W}, 3], got {tuple(u8.shape)}")
     with torch.cuda.device(t.device):
         _lib.call("tmae_tile_blend", t.data_ptr(), g.H, g.W, g.S, g.O, _p(f32), _p(u8), _stream())
+    return (f32, u8) if out == "both" else (f32 if out == "f32" else u8)
+
+
+TILE_CROP_DESC = 8  # int32 per window descriptor (TL_DESC of csrc/tile.hip): H, W, y0, x0, map_base, three unused
+
+
+def tile_blend_crops(tiles, images, windows, size, O: int, out="f32", out_f32=None, out_u8=None):
+    """R windows of one size out of tile_blend's image without the tiles they do not touch (region decode, DESIGN.md
+    §3.16), one launch.  tiles f32 [N, 3, S, S]: a compact buffer of decoded tiles, of any number of images in any
+    order; images: per image (H, W, slots), slots[t] = the position of its tile t in tiles, -1 where the tile is
+    not there; windows: R triples (image index, x0, y0); size = (w, h).  -> f32 [R, 3, h, w] (out="f32"), uint8
+    [R, h, w, 3] ("u8") or the pair ("both"), each window equal to tile_blend(all tiles of its image)[..., y0:y0 + h,
+    x0:x0 + w] bit for bit.  Every window is checked against its image and every tile it needs
+    (tiling.region_tiles) against the buffer, on the host, before anything is uploaded.  out_f32= / out_u8= take
+    preallocated outputs."""
+    from .tiling import grid, region_tiles
+
+    if out not in ("f32", "u8", "both"):
+        raise ValueError(f"tile_blend_crops: out must be 'f32', 'u8' or 'both', got {out!r}")
+    t = _need(tiles, torch.float32, "tiles")
+    if t.dim() != 4 or t.shape[0] < 1 or t.shape[1] != 3 or t.shape[2] != t.shape[3]:
+        raise ValueError(f"tile_blend_crops: tiles must be f32 [N >= 1, 3, S, S], got {tuple(t.shape)}")
+    N, S = int(t.shape[0]), int(t.shape[2])
+    w, h = int(size[0]), int(size[1])
+    images, windows = list(images), list(windows)
+    if not windows:
+        raise ValueError("tile_blend_crops: no windows")
+    grids, bases, slot_map = [], [], []
+    for i, (H, W, slots) in enumerate(images):
+        g = grid(H, W, S, O)
+        slots = [int(s) for s in slots]
+        if len(slots) != g.T:
+            raise ValueError(f"tile_blend_crops: image {i}: {len(slots)} slots, but {g.H}x{g.W} at tile size {g.S}, "
+                             f"overlap {g.O} has {g.ny} x {g.nx} = {g.T} tiles")
+        if any(not -1 <= s < N for s in slots):
+            raise ValueError(f"tile_blend_crops: image {i}: slots must be -1 or one of the buffer's {N}")
+        grids.append(g)
+        bases.append(len(slot_map))
+        slot_map += slots
+    R = len(windows)
+    desc = []
+    for r, (i, x0, y0) in enumerate(windows):
+        i = int(i)
+        if not 0 <= i < len(grids):
+            raise ValueError(f"tile_blend_crops: window {r}: image {i} outside 0..{len(grids) - 1}")
+        g = grids[i]
+        try:
+            need = region_tiles(g, x0, y0, w, h)
+        except ValueError as e:
+            raise ValueError(f"tile_blend_crops: window {r}: {e}") from None
+        for k in need:
+            if slot_map[bases[i] + k] < 0:
+                raise ValueError(f"tile_blend_crops: window {r}: needs tile {k} of image {i}, which has no slot")
+        desc += [g.H, g.W, int(y0), int(x0), bases[i]] + [0] * (TILE_CROP_DESC - 5)
+    f32 = u8 = None
+    if out in ("f32", "both"):
+        f32 = out_f32 if out_f32 is not None else torch.empty((R, 3, h, w), dtype=torch.float32, device=t.device)
+        if tuple(_need(f32, torch.float32, "out_f32").shape) != (R, 3, h, w):
+            raise ValueError(f"tile_blend_crops: out_f32 must be [{R}, 3, {h}, {w}], got {tuple(f32.shape)}")
+    if out in ("u8", "both"):
+        u8 = out_u8 if out_u8 is not None else torch.empty((R, h, w, 3), dtype=torch.uint8, device=t.device)
+        if tuple(_need(u8, torch.uint8, "out_u8").shape) != (R, h, w, 3):
+            raise ValueError(f"tile_blend_crops: out_u8 must be [{R}, {h}, {w}, 3], got {tuple(u8.shape)}")
+    # the descriptors, then the maps: one upload
+    table = torch.tensor(desc + slot_map, dtype=torch.int32).to(t.device)
+    with torch.cuda.device(t.device):
+        _lib.call("tmae_tile_blend_crops", t.data_ptr(), N, table.data_ptr() + 4 * len(desc), len(slot_map),
+                  table.data_ptr(), R, h, w, S, int(O), _p(f32), _p(u8), _stream())
     return (f32, u8) if out == "both" else (f32 if out == "f32" else u8)

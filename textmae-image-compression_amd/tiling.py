@@ -16,6 +16,8 @@ stride = S - O:
   * a pixel's column tiles: tx_hi = min(x // stride, nx - 1), and tx_hi - 1 as well when tx_hi > 0 and
     x - tx_hi * stride < O.  Rows the same.
 
+``region_tiles`` names the tiles a window of the image needs (region decode).
+
 ``tile_cut_host`` / ``tile_blend_host`` restate the two kernels in f64 numpy, straight from the lines above; the
 tests use them as the oracle.  Nothing here touches the device.
 """
@@ -82,6 +84,21 @@ def covering(c: int, n: int, stride: int, O: int):
     """tile indices along one axis that cover coordinate c, ascending"""
     hi = min(c // stride, n - 1)
     return [hi - 1, hi] if hi > 0 and c - hi * stride < O else [hi]
+
+
+def region_tiles(g: Grid, x0, y0, w, h):
+    """ascending tile indices whose blend contributes to any pixel of the window [x0, x0 + w) x [y0, y0 + h) of grid
+    g.  covering() grows with the coordinate, so per axis the tiles are the contiguous range from
+    covering(first)[0] to covering(last)[-1], and the result is the row-major rectangle of the two ranges.
+    ValueError for an empty window or one that is not wholly inside the image."""
+    x0, y0, w, h = int(x0), int(y0), int(w), int(h)
+    if w < 1 or h < 1:
+        raise ValueError(f"window of {w}x{h} pixels: both sizes must be >= 1")
+    if x0 < 0 or y0 < 0 or x0 + w > g.W or y0 + h > g.H:
+        raise ValueError(f"window {w}x{h} at ({x0}, {y0}) is not inside the image of {g.W}x{g.H} pixels")
+    tx0, tx1 = covering(x0, g.nx, g.stride, g.O)[0], covering(x0 + w - 1, g.nx, g.stride, g.O)[-1]
+    ty0, ty1 = covering(y0, g.ny, g.stride, g.O)[0], covering(y0 + h - 1, g.ny, g.stride, g.O)[-1]
+    return [ty * g.nx + tx for ty in range(ty0, ty1 + 1) for tx in range(tx0, tx1 + 1)]
 
 
 def tile_cut_host(img, S, O) -> np.ndarray:

@@ -483,3 +483,201 @@ def test_guards_reject_unwritten_row_and_row_past_m():
     g.buf[g.GR + c.rows, g.GC:g.GC + c.C] = g.block()[c.rows - 1]
     with pytest.raises(AssertionError, match="guard"):
         gk.check("past_m", g, ref, bound, log=False)
+
+
+# ====================================================================================== forward entropy models, coding
+# tests/entropy_check.py: a torch-f32 restatement of each kernel fits its bound, each fault is rejected, every case
+# holds the classes it is there for, nothing is skipped.
+import entropy_check as ek  # noqa: E402
+from oracle import coding_oracle as co  # noqa: E402
+from oracle import mcm_oracle as mo  # noqa: E402
+
+
+def test_model_table_is_the_models(tmae):
+    from textmae_amd.entropy import get_scale_table
+
+    t = ek.model_table()
+    assert torch.equal(t, get_scale_table()) and t.numel() == 64
+    assert float(t[0]) == float(torch.tensor(0.11, dtype=F32))  # why the unbounded-sigma fault needs ek.low_table()
+
+
+def _gcf_run(shape, training, yt, code, mutant=None, table=None, yhat32=True):
+    c = ek.gcf_case(shape, ek.model_table() if table is None else table)
+    out, p = ek.gcf_reference(c, training, yt, code)
+    o = ek.gcf_outputs(c, yt, code, yhat32=yhat32)
+    ek.gcf_emulate(c, ek.gcf_inputs(c, training), o, code, mutant)
+    return c, out, p, o
+
+
+@pytest.mark.parametrize("yt", DTYPES)
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("shape", list(ek.GCF_SHAPES))
+def test_gcf_restatement_fits(shape, training, yt):
+    c, out, p, o = _gcf_run(shape, training, yt, code=not training)
+    r = ek.gcf_check("gcf", o, out, log=False)
+    print(shape, training, yt, r)
+    assert p.skipped == 0 and max(r.values()) <= 1.0
+    assert r["yhat32"] == 0.0 and (yt == BF16 or r["yhat"] == 0.0)
+    # where the likelihood is below 1e-4 and not clamped the bound is a relative one: the issue measured 2.8e-5
+    sel = (p.raw.v >= ek.LIK_MIN) & (p.raw.v < 1e-4)
+    assert float((p.raw.e[sel] / p.raw.v[sel]).max()) <= 1e-4
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("shape", list(ek.GCF_SHAPES) + ["flat", "flat_no_means"])
+def test_gcf_census(shape, training):
+    """every GaussianConditional case holds at least 4 elements of every class (counts beside ek.GCF_SEEDS)"""
+    t = ek.model_table()
+    if shape.startswith("flat"):
+        el = ek.flat_case(t)
+        cen = ek.gc_census(el.y, el.mu if shape == "flat" else None, el.sigma, el.noise if training else None, t)
+        total = el.y.numel()
+    else:
+        c = ek.gcf_case(shape, t)
+        cen = ek.gc_census(ek.gcf_slices(c, c.y), c.mu, c.sigma, ek.gcf_slices(c, c.noise) if training else None, t)
+        total = c.sigma.numel()
+        assert total <= 290 * 64
+    print(shape, "train" if training else "eval", total, cen)
+    for k, v in cen.items():
+        if shape == "flat_no_means" and (k.startswith("tie_") or k == "sign_zero"):
+            continue  # planted against mu; without means round(x) has its own zeros, counted below
+        assert v >= 4, (k, v)
+    assert 0.15 <= cen["clamped"] / total <= 0.4 and 0.2 <= (cen["clamped"] + cen["low"]) / total <= 0.5
+
+
+GCF_REJECTS = {  # mutant: (shape, training, outputs that must reject it)
+    "cancelling": ("ragged_pass", True, ["lik"]), "yoff": ("sub_pass", True, ["lik", "yhat", "yhat32"]),
+    "ld_swap": ("sub_pass", False, ["yhat", "yhat32"]), "nchw_transposed": ("sub_pass", True, ["lik"]),
+    "half_away": ("sub_pass", False, ["yhat", "yhat32", "sym"]), "lt": ("sub_pass", False, ["idx"]),
+    "unbounded_sigma": ("sub_pass", False, ["idx"]), "order_swap": ("sub_pass", False, ["sym", "idx"]),
+    "no_clamp": ("sub_pass", True, ["lik"])}
+
+
+@pytest.mark.parametrize("mutant", ek.GCF_MUTANTS)
+def test_gcf_rejects(mutant):
+    shape, training, outputs = GCF_REJECTS[mutant]
+    table = ek.low_table() if mutant == "unbounded_sigma" else None
+    c, out, p, o = _gcf_run(shape, training, F32, code=not training, mutant=mutant, table=table)
+    for k in outputs:
+        with pytest.raises(AssertionError):
+            if k in ("sym", "idx"):
+                ek.check_exact(k, getattr(o, k), out[k], log=False)
+            else:
+                gk.check(k, getattr(o, k), *out[k], log=False)
+    if mutant == "cancelling":  # the older metric passes it forty times under its bound; per element a fifth fails
+        got, (ref, bound) = o.lik.result(), out["lik"]
+        assert old_metric(got, ref) < 1e-6
+        share = float(((got - ref).abs() > bound).double().mean())
+        print("cancelling form: rejected share of the buffer", share)
+        assert share > 0.05
+    if mutant == "unbounded_sigma":  # against the model's table the fault is no fault: table[0] == 0.11f
+        c, out, p, o = _gcf_run(shape, training, F32, code=True, mutant=mutant)
+        ek.check_exact("idx", o.idx, out["idx"], log=False)
+
+
+@pytest.mark.parametrize("means", [True, False])
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("bound", [0.11, 0.25])
+def test_flat_restatement_fits(bound, training, means):
+    el = ek.flat_case(ek.model_table())
+    (ref, b), xt, r = ek.flat_reference(el, training, means, bound)
+    lik = mo.gaussian_conditional(el.y, el.sigma, el.mu if means else torch.zeros_like(el.mu), el.noise if training else None,
+                                  bound)
+    print(bound, training, means, fits("lik", lik.reshape(1, -1), ref, b))
+    rejects("lik", gk.written(lik.clamp_min(1e-8).reshape(1, -1)), ref, b)
+
+
+# ------------------------------------------------------------------------------------ EntropyBottleneck forward
+@pytest.fixture(scope="module")
+def ebs(tmae):
+    return {C: gk.eb_module(tmae, C) for C in (5, 70, 90)}
+
+
+EBF_CASES = [(C, HW, tr) for (C, HW) in ek.EBF_SEEDS for tr in (True, False)]
+
+
+@pytest.mark.parametrize("C,HW,training", EBF_CASES)
+def test_ebf_restatement_fits_and_census(ebs, C, HW, training):
+    c = ek.ebf_case(ebs[C], HW)
+    out, p = ek.ebf_reference(c, training)
+    cen = ek.ebf_census(c, p)
+    print(C, HW, "train" if training else "eval", c.N * C, cen)
+    for k in ("clamped", "below_median", "above_median", "sum_negative", "sum_positive"):
+        assert cen[k] >= 4, (k, cen)
+    assert p.skipped == 0 and int((c.sd[gk.EB_PRE + "_matrix2"] > 20).sum()) == 1
+    lik, zhat = ek.ebf_restate(c, training)
+    print("ratio", fits("lik", lik.reshape(1, -1), *out["lik"]))
+    for zt in DTYPES:
+        o2, _ = ek.ebf_reference(c, training, zt)
+        fits("zhat", zhat, *o2["zhat"], dtype=zt)
+    assert fits("zhat", zhat, *out["zhat"]) == 0.0
+    # faults: the median from quantile 0 (likelihood in eval, zhat and symbols always), the clamp dropped
+    lik0, zhat0 = ek.ebf_restate(c, training, med_index=0)
+    rejects("zhat", gk.written(zhat0), *out["zhat"])
+    bad, _ = ek.ebf_reference(c, training, med_index=0)
+    assert int((bad["sym"] != out["sym"]).sum()) > 0
+    if not training:
+        rejects("lik", gk.written(lik0.reshape(1, -1)), *out["lik"])
+    raw, _ = ek.ebf_restate(c, training, clamp=False)
+    rejects("lik", gk.written(raw.reshape(1, -1)), *out["lik"])
+
+
+@pytest.mark.parametrize("C", [5, 90])
+def test_eb_aux_loss_reference_fits(ebs, C):
+    sd = {gk.EB_PRE + k: v.detach().clone().float() for k, v in ebs[C].state_dict().items()}
+    ref, bound = ek.eb_aux_loss_reference(sd)
+    v = mo.eb_aux_loss(sd, gk.EB_PRE)
+    assert abs(float(mo.eb_aux_loss({k: t.double() for k, t in sd.items()}, gk.EB_PRE)) - float(ref)) <= 1e-10 * float(ref)
+    print(C, fits("aux", v.reshape(1, 1), ref, bound))
+    # the any-order sum rule over 3 C + 2 = 272 roundings alone is 3.3e-5 of sum |t| at C = 90
+    rejects("aux", gk.written((v * (1 + 1e-4)).reshape(1, 1)), ref, bound)
+
+
+def test_pmf_references_fit(ebs):
+    sd = {gk.EB_PRE + k: v.detach().clone().float() for k, v in ebs[5].state_dict().items()}
+    t = ek.model_table()
+    tb = ek.pmf_tables(sd, t)
+    pmf, tail, center, L = co.gc_pmf(t)
+    (ref, b), (tref, tb_) = ek.gc_pmf_reference(t, center, L)
+    print("gc pmf", fits("pmf", pmf, ref, b), fits("tail", tail.reshape(1, -1), tref, tb_))
+    shifted = torch.roll(pmf, 1, 1)  # the centre off by one
+    rejects("pmf", gk.written(shifted), ref, b)
+    pmf, tail, start, L = co.eb_pmf(sd, gk.EB_PRE)
+    assert L == tb.eb_length and torch.equal(start, tb.start)
+    (ref, b), (tref, tb_) = ek.eb_pmf_reference(sd, start, L)
+    print("eb pmf", fits("pmf", pmf, ref, b), fits("tail", tail.reshape(1, -1), tref, tb_))
+    rejects("pmf", gk.written(torch.roll(pmf, 1, 1)), ref, b)  # the start off by one
+    # quantiles 1 .. 3 samples from the median: lengths differ, tails are real masses; upstream takes the PADDED
+    # range's last sample, so the tail from each channel's own last sample is a fault
+    sd = ek.narrow_quantiles(sd)
+    pmf, tail, start, L = co.eb_pmf(sd, gk.EB_PRE)
+    (ref, b), (tref, tb_) = ek.eb_pmf_reference(sd, start, L)
+    print("eb pmf narrow", L, tail, fits("pmf", pmf, ref, b), fits("tail", tail.reshape(1, -1), tref, tb_))
+    assert float(tail.min()) > 1e-30
+    q = sd[gk.EB_PRE + "quantiles"]
+    med = q[:, 0, 1]
+    own = (torch.ceil(med - q[:, 0, 0]) + torch.ceil(q[:, 0, 2] - med)).reshape(-1, 1, 1)  # index of the own last sample
+    assert int((own.flatten() < L - 1).sum()) >= 2
+    lo = mo.eb_logits(sd, gk.EB_PRE, start.reshape(-1, 1, 1) - 0.5)
+    up = mo.eb_logits(sd, gk.EB_PRE, start.reshape(-1, 1, 1) + own + 0.5)
+    rejects("tail", gk.written((torch.sigmoid(lo) + torch.sigmoid(-up)).reshape(1, -1)), tref, tb_)
+
+
+# ------------------------------------------------------------------------------------ integer outputs
+def test_guarded_int_and_permutation_reference():
+    p = ek.perm_case()
+    inv = ek.invert_reference(p)
+    assert torch.equal(torch.gather(inv, 1, p), torch.arange(p.shape[1]).expand_as(p))
+    g = ek.GuardedInt(3, 100, ek.I64, init=inv)
+    assert ek.check_exact("inv", g, inv, log=False) == 0.0
+    g.buf[0, 0] = 7
+    with pytest.raises(AssertionError, match="guard"):
+        ek.check_exact("inv", g, inv, log=False)
+    g = ek.GuardedInt(3, 100, ek.I64, init=inv)
+    g.block()[1, 5] += 1
+    with pytest.raises(AssertionError, match="differ"):
+        ek.check_exact("inv", g, inv, log=False)
+    p2 = p.clone()
+    p2[1, 3], p2[1, 50] = 100, -1  # out of range, and -1: the two slots they would have named keep the sentinel
+    inv2 = ek.invert_reference(p2)
+    assert int((inv2 == ek.SENTINEL).sum()) == 2 and int((inv2[[0, 2]] == ek.SENTINEL).sum()) == 0

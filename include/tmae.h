@@ -316,6 +316,25 @@ int tmae_gc_dequantize(const int* symbols, const float* mu, long long ms_stride,
                        int nslices, int sw, int yoff, void* yhat, int yhat_dtype, int ld_yhat, float* yhat32, int ld32,
                        void* stream);
 
+/* The three coding kernels above with a per-image quantiser step on y (the reference has no
+ * counterpart).  q: device int32 [n], one ladder position per image in -32..32, or NULL = all zero;
+ * delta(q) = F[q mod 8] * 2^floor(q / 8), F[k] = the f32 nearest to 2^(k/8).  Per element, every operation rounded
+ * to f32 on its own (no contraction):
+ *   qi = rint((y - mu) / delta), symbols = (int)qi, y_hat = fl(fl(qi * delta) + mu) (both the encode and the decode
+ *   side), s = max(sigma / delta, scale_bound), indexes = build_indexes(s),
+ *   likelihood (optional, lik may be NULL) = max(Phi((0.5 - |qi|) / s) - Phi((-0.5 - |qi|) / s), 1e-9).
+ * Layouts and the other arguments as in the functions above; at q = 0 symbols, indexes and y_hat are bitwise theirs. */
+int tmae_gc_slices_code_q(const float* y, int ldy, int yoff, const float* mu, const float* sigma, long long ms_stride,
+                          int ld_ms, float* lik, int Mtot, void* yhat, int yhat_dtype, int ld_yhat, float* yhat32,
+                          int ld32, int n, int HW, int nslices, int sw, int* symbols, int* indexes,
+                          const float* scale_table, int nscale, float scale_bound, const int* q, void* stream);
+int tmae_gc_indexes_q(const float* sigma, long long ms_stride, int ld_ms, int n, int HW, int nslices, int sw,
+                      const float* scale_table, int nscale, float scale_bound, int* indexes, const int* q,
+                      void* stream);
+int tmae_gc_dequantize_q(const int* symbols, const float* mu, long long ms_stride, int ld_ms, int n, int HW,
+                         int nslices, int sw, int yoff, void* yhat, int yhat_dtype, int ld_yhat, float* yhat32,
+                         int ld32, const int* q, void* stream);
+
 /* GaussianConditional.update (update_scale_table): pmf[n][max_length], tail[n] for the CDF builder */
 int tmae_gc_pmf(const float* scale_table, const int* pmf_center, int n, int max_length, float* pmf, float* tail,
                 void* stream);

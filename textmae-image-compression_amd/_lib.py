@@ -151,6 +151,10 @@ SIGNATURES = {
     "tmae_gc_slices_code": [P, I, I, P, P, LL, I, P, I, P, I, I, P, I, I, I, I, I, P, P, P, I, P],
     "tmae_gc_indexes": [P, LL, I, I, I, I, I, P, I, F, P, P],
     "tmae_gc_dequantize": [P, P, LL, I, I, I, I, I, I, P, I, I, P, I, P],
+    # the same three with a per-image quantiser step
+    "tmae_gc_slices_code_q": [P, I, I, P, P, LL, I, P, I, P, I, I, P, I, I, I, I, I, P, P, P, I, F, P, P],
+    "tmae_gc_indexes_q": [P, LL, I, I, I, I, I, P, I, F, P, P, P],
+    "tmae_gc_dequantize_q": [P, P, LL, I, I, I, I, I, I, P, I, I, P, I, P, P],
     "tmae_gc_pmf": [P, P, I, I, P, P, P],
     "tmae_eb_pmf": [ctypes.POINTER(EBParams), P, P, I, I, P, P, P],
     "tmae_eb_symbols": [P, ctypes.POINTER(EBParams), P, I, I, I, P, P],

@@ -25,6 +25,10 @@ one image coded at its own resolution as overlapping tiles: the sections of the 
 and a table of record lengths (``MCM.encode_image`` / ``decode_image``).  ``read_image_index`` /
 ``read_tiles`` read such a file's header and table and then single tiles, from bytes or from a file object, without
 touching the other tiles (``MCM.decode_region`` / ``decode_crops``).
+
+Blobs and files whose y latents were coded at a quantiser step other than 1 (``q=`` of the model's methods, DESIGN.md
+§3.17) carry the magics b"TQC" / b"TQT" and the ladder position q; every reader here takes both kinds and returns q
+as the last field of its tuple (0 for TMC / TMT).  ``qstep`` is the ladder.
 """
 from __future__ import annotations
 
@@ -36,12 +40,44 @@ import numpy as np
 MAGIC = b"TMC"
 VERSION = 1
 HEADER_BYTES = 16
+# the same blob coded at a quantiser step other than 1: the 16 TMC header bytes, then one word
+# holding the ladder position q as int8 and three zero bytes, then ids, z and y as in TMC.  q = 0 is always TMC.
+QMAGIC = b"TQC"
+QHEADER_BYTES = 20
+Q_MIN, Q_MAX = -32, 32
+# F[k] = the f32 nearest to 2^(k/8), the literals of tmae_qstep (csrc/common.h)
+QSTEP_F = (1.0, 1.09050775, 1.18920708, 1.29683959, 1.41421354, 1.54221082, 1.68179286, 1.8340081)
 MAX_L = 1024       # IDS_MAXL of the kernels
 MAX_LANE_LOG2 = 6  # lanes <= 64 (coder.check_lanes)
 _HEADER = struct.Struct("<3sBHHBBHHH")
 
 # status words of unpack (tmae_ids_unpack)
 IDS_STATUS = {1: "patch id outside the image", 2: "duplicate patch id", 3: "non-zero padding bits"}
+
+
+def check_q(q, who="q") -> int:
+    """q as an int in Q_MIN..Q_MAX, ValueError otherwise"""
+    v = int(q)
+    if v != q or not Q_MIN <= v <= Q_MAX:
+        raise ValueError(f"{who} = {q!r} outside {Q_MIN}..{Q_MAX} (integer positions on the quantiser step ladder)")
+    return v
+
+
+def qstep(q) -> np.float32:
+    """the quantiser step of ladder position q: F[q mod 8] * 2^floor(q / 8) as f32, 1/16 .. 16, qstep(0) = 1; the
+    mirror of tmae_qstep (csrc/common.h), which the kernels evaluate themselves"""
+    v = check_q(q)
+    return np.ldexp(np.float32(QSTEP_F[v % 8]), v // 8).astype(np.float32)
+
+
+def _read_q(byte, what, plain):
+    """the int8 ladder position of a TQC / TQT header: never 0 (that is written as `plain`), within the ladder"""
+    q = byte - 256 if byte >= 128 else byte
+    if q == 0:
+        raise ValueError(f"{what} stream with q = 0: a step of 1 is written as {plain}")
+    if not Q_MIN <= q <= Q_MAX:
+        raise ValueError(f"{what} stream with q = {q}: the ladder is {Q_MIN}..{Q_MAX}")
+    return q
 
 
 class Blob(NamedTuple):
@@ -55,6 +91,7 @@ class Blob(NamedTuple):
     ids: np.ndarray          # uint32 [W] view
     z: memoryview
     y: memoryview
+    q: int = 0               # ladder position of the y quantiser step (0: a TMC blob, else a TQC one)
 
     @property
     def num_patches(self) -> int:
@@ -89,8 +126,10 @@ def _check_geometry(img_size, K, patch):
     return L
 
 
-def pack_header(img_size, num_keep_patches, patch_size, lanes=1, z_lanes=1, z_words=0, orig_size=None) -> bytes:
-    """the 16 header bytes; z_words = length of the z record in 32-bit words, orig_size = (width, height) or None"""
+def pack_header(img_size, num_keep_patches, patch_size, lanes=1, z_lanes=1, z_words=0, orig_size=None, q=0) -> bytes:
+    """the 16 header bytes (q = 0, TMC) or the 20 of a TQC blob; z_words = length of the z record in 32-bit words,
+    orig_size = (width, height) or None"""
+    q = check_q(q)
     img_size, K, patch, z_words = int(img_size), int(num_keep_patches), int(patch_size), int(z_words)
     if not (0 < img_size < 1 << 16 and 0 < patch < 1 << 8):
         raise ValueError(f"img_size {img_size} / patch_size {patch} do not fit the header (u16 / u8)")
@@ -101,11 +140,15 @@ def pack_header(img_size, num_keep_patches, patch_size, lanes=1, z_lanes=1, z_wo
     if not (0 <= w < 1 << 16 and 0 <= h < 1 << 16):
         raise ValueError(f"original size {(w, h)} does not fit the header's u16 fields")
     nib = _log2_lanes(lanes, "lanes") | _log2_lanes(z_lanes, "z_lanes") << 4
+    if q:
+        return _HEADER.pack(QMAGIC, VERSION, img_size, K, patch, nib, z_words, w, h) + struct.pack("<bxxx", q)
     return _HEADER.pack(MAGIC, VERSION, img_size, K, patch, nib, z_words, w, h)
 
 
-def assemble(img_size, num_keep_patches, patch_size, lanes, z_lanes, orig_size, ids_words, z_record, y_record) -> bytes:
-    """one blob from its parts; ids_words: uint32-compatible [W] array (pack_ids_host / ops.ids_pack of one image)"""
+def assemble(img_size, num_keep_patches, patch_size, lanes, z_lanes, orig_size, ids_words, z_record, y_record,
+             q=0) -> bytes:
+    """one blob from its parts; ids_words: uint32-compatible [W] array (pack_ids_host / ops.ids_pack of one image);
+    q: the ladder position the y record was coded at (0: a TMC blob, byte for byte; else TQC)"""
     L = _check_geometry(int(img_size), int(num_keep_patches), int(patch_size))
     ids = np.ascontiguousarray(ids_words).view(np.uint32).reshape(-1).astype("<u4", copy=False)
     if ids.size != id_words(L, num_keep_patches):
@@ -113,36 +156,45 @@ def assemble(img_size, num_keep_patches, patch_size, lanes, z_lanes, orig_size, 
     z, y = bytes(z_record), bytes(y_record)
     if len(z) % 4 or len(y) % 4:
         raise ValueError(f"records are whole 32-bit words (z {len(z)} bytes, y {len(y)} bytes)")
-    return pack_header(img_size, num_keep_patches, patch_size, lanes, z_lanes, len(z) // 4, orig_size) \
+    return pack_header(img_size, num_keep_patches, patch_size, lanes, z_lanes, len(z) // 4, orig_size, q) \
         + ids.tobytes() + z + y
 
 
 def parse(blob) -> Blob:
     """header fields and views of the id words, the z record and the y record; ValueError on a blob that is not a
-    well-formed version-1 container (the records themselves are checked by the coder)"""
+    well-formed version-1 TMC or TQC container (the records themselves are checked by the coder)"""
     mv = memoryview(blob).cast("B") if not isinstance(blob, memoryview) else blob.cast("B")
     n = len(mv)
     if n < HEADER_BYTES:
         raise ValueError(f"{n} bytes: shorter than the {HEADER_BYTES}-byte header")
     magic, version, img_size, K, patch, nib, z_words, w, h = _HEADER.unpack_from(mv, 0)
-    if magic != MAGIC:
+    if magic not in (MAGIC, QMAGIC):
         raise ValueError(f"not a TMC bitstream (magic {bytes(magic)!r})")
     if version != VERSION:
         raise ValueError(f"container version {version}, this reader knows version {VERSION}")
     if n % 4:
         raise ValueError(f"{n} bytes: not a whole number of 32-bit words")
+    q, hb = 0, HEADER_BYTES
+    if magic == QMAGIC:
+        hb = QHEADER_BYTES
+        if n < hb:
+            raise ValueError(f"{n} bytes: shorter than the {hb}-byte TQC header")
+        q = _read_q(mv[16], "TQC", "TMC")
+        if mv[17] or mv[18] or mv[19]:
+            raise ValueError(f"TQC stream: padding bytes 17-19 hold {bytes(mv[17:20]).hex()}, must be zero")
     ll, zl = nib & 15, nib >> 4
     if ll > MAX_LANE_LOG2 or zl > MAX_LANE_LOG2:
         raise ValueError(f"lane fields 2^{ll} / 2^{zl}: at most 2^{MAX_LANE_LOG2} lanes")
     L = _check_geometry(img_size, K, patch)
     W = id_words(L, K)
-    need = HEADER_BYTES + 4 * (W + z_words + 2)
+    need = hb + 4 * (W + z_words + 2)
     if n < need:
         raise ValueError(f"{n} bytes: header + {W} id words + {z_words} z words + at least 2 y words take {need}")
-    z0 = HEADER_BYTES + 4 * W
+    z0 = hb + 4 * W
     y0 = z0 + 4 * z_words
-    ids = np.frombuffer(mv, dtype="<u4", count=W, offset=HEADER_BYTES)
-    return Blob(img_size, K, patch, 1 << ll, 1 << zl, (w, h) if (w, h) != (0, 0) else None, ids, mv[z0:y0], mv[y0:])
+    ids = np.frombuffer(mv, dtype="<u4", count=W, offset=hb)
+    return Blob(img_size, K, patch, 1 << ll, 1 << zl, (w, h) if (w, h) != (0, 0) else None, ids, mv[z0:y0], mv[y0:],
+                q)
 
 
 # ------------------------------------------------------------------------------------ tiled images: b"TMT", version 1
@@ -158,7 +210,11 @@ def parse(blob) -> Blob:
 #           20-23  T u32 = nx * ny of the fields above
 #           then   T table entries: z_words u32, y_words u32
 #           then   per tile, in order: W = id_words(L, K) id words, the z record, the y record
+#
+# b"TQT", version 1: the same file coded at one quantiser step other than 1: byte 18 holds the ladder
+# position q as int8, byte 19 stays zero, everything else as above.  q = 0 is always TMT.
 IMAGE_MAGIC = b"TMT"
+IMAGE_QMAGIC = b"TQT"
 IMAGE_VERSION = 1
 IMAGE_HEADER_BYTES = 24
 _IMAGE_HEADER = struct.Struct("<3sBHHBBHHHHHI")
@@ -178,6 +234,7 @@ class ImageBlob(NamedTuple):
     ids: list                # T uint32 [W] views
     z: list                  # T memoryviews
     y: list
+    q: int = 0               # ladder position of the y quantiser step of every tile (0: a TMT file, else TQT)
 
     @property
     def num_patches(self) -> int:
@@ -189,10 +246,13 @@ class ImageBlob(NamedTuple):
 
 
 def assemble_image(img_size, num_keep_patches, patch_size, lanes, z_lanes, overlap, width, height, chunk, ids_words,
-                   z_records, y_records) -> bytes:
+                   z_records, y_records, q=0) -> bytes:
     """one TMT file from its parts; ids_words: uint32-compatible [T, W] (ops.ids_pack of the tiles), z_records /
-    y_records: T byte strings each (compress_batch's records of the tiles, in tile order)"""
+    y_records: T byte strings each (compress_batch's records of the tiles, in tile order); q: the ladder position
+    all tiles were coded at (0: a TMT file, byte for byte; else TQT)"""
     from .tiling import grid
+
+    q = check_q(q)
 
     img_size, K, patch = int(img_size), int(num_keep_patches), int(patch_size)
     overlap, width, height, chunk = int(overlap), int(width), int(height), int(chunk)
@@ -217,9 +277,21 @@ def assemble_image(img_size, num_keep_patches, patch_size, lanes, z_lanes, overl
         table.append(struct.pack("<II", len(z) // 4, len(y) // 4))
         body += [ids[t].tobytes(), z, y]
     nib = _log2_lanes(lanes, "lanes") | _log2_lanes(z_lanes, "z_lanes") << 4
-    head = _IMAGE_HEADER.pack(IMAGE_MAGIC, IMAGE_VERSION, img_size, K, patch, nib, overlap, width, height, chunk, 0,
-                              g.T)
+    head = _IMAGE_HEADER.pack(IMAGE_QMAGIC if q else IMAGE_MAGIC, IMAGE_VERSION, img_size, K, patch, nib, overlap,
+                              width, height, chunk, q & 0xFF, g.T)
     return head + b"".join(table) + b"".join(body)
+
+
+def _image_q(magic, word):
+    """bytes 18-19 of a TMT / TQT header (as the u16 `word`) -> q: TMT holds zero there, TQT q as int8 then zero"""
+    if magic == IMAGE_MAGIC:
+        if word:
+            raise ValueError(f"reserved bytes 18-19 hold {word:#06x}, must be zero")
+        return 0
+    q = _read_q(word & 0xFF, "TQT", "TMT")
+    if word >> 8:
+        raise ValueError(f"TQT stream: padding byte 19 holds {word >> 8:#04x}, must be zero")
+    return q
 
 
 def parse_image(blob) -> ImageBlob:
@@ -232,7 +304,7 @@ def parse_image(blob) -> ImageBlob:
     if n < IMAGE_HEADER_BYTES:
         raise ValueError(f"{n} bytes: shorter than the {IMAGE_HEADER_BYTES}-byte header")
     magic, version, S, K, patch, nib, O, width, height, chunk, zero, T = _IMAGE_HEADER.unpack_from(mv, 0)
-    if magic != IMAGE_MAGIC:
+    if magic not in (IMAGE_MAGIC, IMAGE_QMAGIC):
         raise ValueError(f"not a TMT bitstream (magic {bytes(magic)!r})")
     if version != IMAGE_VERSION:
         raise ValueError(f"container version {version}, this reader knows version {IMAGE_VERSION}")
@@ -248,8 +320,7 @@ def parse_image(blob) -> ImageBlob:
         raise ValueError(f"image size {width}x{height}: width and height must be >= 1")
     if chunk == 0:
         raise ValueError("chunk 0: the encoder's tile batch must be >= 1")
-    if zero:
-        raise ValueError(f"reserved bytes 18-19 hold {zero:#06x}, must be zero")
+    q = _image_q(magic, zero)
     if T > MAX_TILES:
         raise ValueError(f"{T} tiles: at most {MAX_TILES}")
     g = grid(height, width, S, O)
@@ -275,7 +346,7 @@ def parse_image(blob) -> ImageBlob:
         at = y0 + 4 * int(table[t, 1])
         zs.append(mv[z0:y0])
         ys.append(mv[y0:at])
-    return ImageBlob(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids, zs, ys)
+    return ImageBlob(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids, zs, ys, q)
 
 
 class ImageIndex(NamedTuple):
@@ -295,6 +366,7 @@ class ImageIndex(NamedTuple):
     z_at: np.ndarray
     y_at: np.ndarray
     end_at: np.ndarray
+    q: int = 0               # as ImageBlob.q
 
     @property
     def num_tiles(self) -> int:
@@ -336,7 +408,7 @@ def read_image_index(src) -> ImageIndex:
         raise ValueError(f"{n} bytes: shorter than the {IMAGE_HEADER_BYTES}-byte header")
     magic, version, S, K, patch, nib, O, width, height, chunk, zero, T = _IMAGE_HEADER.unpack(
         read(0, IMAGE_HEADER_BYTES))
-    if magic != IMAGE_MAGIC:
+    if magic not in (IMAGE_MAGIC, IMAGE_QMAGIC):
         raise ValueError(f"not a TMT bitstream (magic {bytes(magic)!r})")
     if version != IMAGE_VERSION:
         raise ValueError(f"container version {version}, this reader knows version {IMAGE_VERSION}")
@@ -352,8 +424,7 @@ def read_image_index(src) -> ImageIndex:
         raise ValueError(f"image size {width}x{height}: width and height must be >= 1")
     if chunk == 0:
         raise ValueError("chunk 0: the encoder's tile batch must be >= 1")
-    if zero:
-        raise ValueError(f"reserved bytes 18-19 hold {zero:#06x}, must be zero")
+    q = _image_q(magic, zero)
     if T > MAX_TILES:
         raise ValueError(f"{T} tiles: at most {MAX_TILES}")
     g = grid(height, width, S, O)
@@ -374,7 +445,7 @@ def read_image_index(src) -> ImageIndex:
     ids_at = np.concatenate([[body0], end_at[:-1]])
     z_at = ids_at + 4 * W
     return ImageIndex(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids_at, z_at, z_at + 4 * table[:, 0],
-                      end_at)
+                      end_at, q)
 
 
 def read_tiles(src, index: ImageIndex, tiles):
@@ -397,12 +468,13 @@ def read_tiles(src, index: ImageIndex, tiles):
 
 
 def tile_blob(parsed: ImageBlob, t: int) -> bytes:
-    """the version-1 TMC blob of tile t of a parsed TMT file (no original size): what MCM.encode_bytes gives for
-    that tile, and what parse() / MCM.decode_bytes read"""
+    """the version-1 TMC blob of tile t of a parsed TMT file, or the TQC blob of a tile of a TQT file (no original
+    size): what MCM.encode_bytes gives for that tile, and what parse() / MCM.decode_bytes read"""
     p = parsed
     if not 0 <= t < p.num_tiles:
         raise ValueError(f"tile {t} outside 0..{p.num_tiles - 1}")
-    return assemble(p.img_size, p.num_keep_patches, p.patch_size, p.lanes, p.z_lanes, None, p.ids[t], p.z[t], p.y[t])
+    return assemble(p.img_size, p.num_keep_patches, p.patch_size, p.lanes, p.z_lanes, None, p.ids[t], p.z[t], p.y[t],
+                    p.q)
 
 
 def pack_ids_host(ids_keep, L: int) -> np.ndarray:

@@ -4,11 +4,16 @@
     python -m textmae_amd.codec decode -c CKPT -d OUT -o PNGS [--original_size]
     python -m textmae_amd.codec encode --tiled [--overlap N] -c CKPT -d FOLDER -o OUT
     python -m textmae_amd.codec decode --region X,Y,W,H -c CKPT -d OUT -o PNGS
+    python -m textmae_amd.codec encode [--tiled] --q N | --target-bytes N ...
 
 ``encode --tiled`` codes every image at its own resolution as overlapping model-sized tiles (MCM.encode_image,
 one ``<name>.tmt`` each); ``decode`` takes ``.tmt`` files next to ``.tmc`` ones and saves them at their native size.
 ``decode --region X,Y,W,H`` saves that window of every ``.tmt`` file instead, reading and decoding only the tiles
 the window needs (MCM.decode_region); ``.tmc`` files beside them decode as before.
+
+``encode --q N`` codes the y latents at the quantiser step 2^(N/8), N in -32..32: larger N, smaller
+files.  ``encode --target-bytes N`` instead picks, per file, the smallest N whose file is at most that many bytes,
+and warns about a file that does not fit even at N = 32.  The files record N; ``decode`` needs no flag.
 
 ``encode`` reads FOLDER through ``data.ImageFolderLoader`` (the test transform: bicubic resize to the model's
 size, scores from ``<FOLDER>_scores/test.pt`` or the device producer) and writes one ``<name>.tmc`` per image,
@@ -39,6 +44,12 @@ def _model(checkpoint, num_keep_patches, input_size, half):
     return model
 
 
+def _warn_target(args, name, blob):
+    if args.target_bytes is not None and len(blob) > args.target_bytes:
+        print(f"Warning: {name}: {len(blob)} bytes at the coarsest step (q = {bitstream.Q_MAX}), above "
+              f"--target-bytes {args.target_bytes}.", file=sys.stderr)
+
+
 @torch.no_grad()
 def encode_tiled(args, model):
     """--tiled: every image at its own resolution (no resize, no loader) -> <name>.tmt, MCM.encode_image"""
@@ -52,7 +63,9 @@ def encode_tiled(args, model):
     nbytes = npixels = 0
     for p in files:
         a = np.array(Image.open(p).convert("RGB"))
-        blob = model.encode_image(a, overlap=args.overlap, lanes=args.lanes, tile_batch=args.batch)
+        blob = model.encode_image(a, overlap=args.overlap, lanes=args.lanes, tile_batch=args.batch, q=args.q,
+                                  target_bytes=args.target_bytes)
+        _warn_target(args, p.name, blob)
         with open(os.path.join(args.output, p.stem + ".tmt"), "wb") as f:
             f.write(blob)
         nbytes += len(blob)
@@ -72,8 +85,10 @@ def encode(args):
     os.makedirs(args.output, exist_ok=True)
     paths, done, nbytes = loader.imgs_path, 0, 0
     for imgs, ori_shapes, scores in loader:  # unshuffled: batch i holds paths[done : done + B]
-        blobs = model.encode_bytes(imgs, scores, lanes=args.lanes, orig_sizes=ori_shapes)
+        blobs = model.encode_bytes(imgs, scores, lanes=args.lanes, orig_sizes=ori_shapes, q=args.q,
+                                   target_bytes=args.target_bytes)
         for p, blob in zip(paths[done:done + len(blobs)], blobs):
+            _warn_target(args, p.name, blob)
             with open(os.path.join(args.output, p.stem + ".tmc"), "wb") as f:
                 f.write(blob)
             nbytes += len(blob)
@@ -147,6 +162,11 @@ def setup_args():
                    help="code every image at its own resolution as overlapping model-sized tiles -> <name>.tmt "
                         "(--batch tiles per device call)")
     q.add_argument("--overlap", type=int, default=32, help="tile overlap in pixels (--tiled), 0..input_size / 2")
+    rate = q.add_mutually_exclusive_group()
+    rate.add_argument("--q", type=int, default=None, metavar="N",
+                      help="quantiser step 2^(N/8) on the y latents, N in -32..32: larger N, smaller files")
+    rate.add_argument("--target-bytes", type=int, default=None, metavar="N", dest="target_bytes",
+                      help="per file, the smallest step whose file is at most N bytes")
     sub.choices["decode"].add_argument("--original_size", action="store_true",
                                        help="save each output resized to the size its file recorded")
     sub.choices["decode"].add_argument("--region", type=_region, default=None, metavar="X,Y,W,H",

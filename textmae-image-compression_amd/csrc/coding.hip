@@ -96,6 +96,206 @@ extern "C" int tmae_gc_dequantize(const int* symbols, const float* mu, long long
   TMAE_LAUNCH_CHECK("tmae_gc_dequantize");
 }
 
+// ------------------------------------------------------------------ per-image quantiser step
+// The three kernels above with y quantised at a step delta(q[image]) of the ladder in common.h: symbols
+// rint((y - mu) / delta), reconstruction fl(fl(qi delta) + mu), entropy model at max(sigma / delta, bound).  The
+// reference has no counterpart.  Encoder and decoder must produce the same bits, and the tests restate the
+// arithmetic in numpy f32, so every operation is rounded on its own: the helpers are compiled with contraction off
+// (the __fmul_rn / __fadd_rn forms of the HIP headers are plain operators, which the default -ffp-contract=fast
+// may still fuse into one fma after inlining; the pragma is what keeps the product rounded).
+struct GcqElem { float qi, yhat, s; };
+
+__device__ __forceinline__ float gcq_recon(float qi, float mv, float delta) {
+#pragma clang fp contract(off)
+  const float p = qi * delta;
+  return p + mv;
+}
+
+__device__ __forceinline__ float gcq_scale(float sv, float delta, float bound) { return fmaxf(sv / delta, bound); }
+
+__device__ __forceinline__ GcqElem gcq_quantize(float yv, float mv, float sv, float delta, float bound) {
+#pragma clang fp contract(off)
+  const float d = yv - mv;
+  const float qi = rintf(d / delta);
+  return GcqElem{qi, gcq_recon(qi, mv, delta), gcq_scale(sv, delta, bound)};
+}
+
+__device__ __forceinline__ int gcq_index(float s, const float* __restrict__ scale_table, int nscale) {
+  int id = nscale - 1;
+  for (int t = 0; t < nscale - 1; ++t) id -= (s <= scale_table[t]) ? 1 : 0;
+  return id;
+}
+
+// the symbol's probability mass under N(0, s): the table entry the coder approximates
+__device__ __forceinline__ float gcq_likelihood(float qi, float s) {
+  const float val = fabsf(qi);
+  const float k = -0.70710678118654752440f;
+  const float up = 0.5f * erfcf(k * ((0.5f - val) / s));
+  const float lo = 0.5f * erfcf(k * ((-0.5f - val) / s));
+  return fmaxf(up - lo, 1e-9f);
+}
+
+// one element per thread (maps past the LDS tile): gc_slices_kernel<YT, true>'s indexing
+template <typename YT>
+__global__ void __launch_bounds__(256)
+gcq_slices_kernel(const float* __restrict__ y, int ldy, int yoff, const float* __restrict__ mu,
+                  const float* __restrict__ sigma, long long ms_stride, int ld_ms, float* __restrict__ lik, int Mtot,
+                  YT* __restrict__ yhat, int ld_yhat, float* __restrict__ yhat32, int ld32, int n, int HW, int nslices,
+                  int sw, int total, int* __restrict__ sym, int* __restrict__ idx,
+                  const float* __restrict__ scale_table, int nscale, float bound, const int* __restrict__ q) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int per_pix = nslices * sw;
+  const int m = i / per_pix, r = i - m * per_pix;
+  const int j = r / sw, c = r - j * sw;
+  const int ch = yoff + j * sw + c;
+  const int b = m / HW, pix = m - b * HW;
+  const float delta = tmae_qstep(q ? q[b] : 0);
+  const size_t ms = j * ms_stride + (size_t)m * ld_ms + c;
+  const GcqElem e = gcq_quantize(y[(size_t)m * ldy + ch], mu[ms], sigma[ms], delta, bound);
+  if (yhat) yhat[(size_t)m * ld_yhat + ch] = to_out<YT>(e.yhat);
+  if (yhat32) yhat32[(size_t)m * ld32 + ch] = e.yhat;
+  if (lik) lik[((size_t)b * Mtot + ch) * HW + pix] = gcq_likelihood(e.qi, e.s);
+  const size_t pos = (size_t)j * n * sw * HW + ((size_t)b * sw + c) * HW + pix;
+  sym[pos] = (int)e.qi;
+  idx[pos] = gcq_index(e.s, scale_table, nscale);
+}
+
+// One 1024-thread workgroup per (image, slice), as gc_slices_tiled_kernel (conv.hip, whose comment gives the
+// reason): y / mu / sigma read and y_hat written channel fastest, then the rounded value and the bounded scale go
+// through LDS and the symbols, indexes and likelihoods are written pixel fastest.  The step is uniform over the
+// workgroup.  Same arithmetic per element as the kernel above.
+constexpr int GCQ_TILE_MAX = 4800;  // HW * (sw + 1) floats per LDS array (2 arrays, 38.4 KB): conv.hip's GC_TILE_MAX
+template <typename YT>
+__global__ void __launch_bounds__(1024)
+gcq_slices_tiled_kernel(const float* __restrict__ y, int ldy, int yoff, const float* __restrict__ mu,
+                        const float* __restrict__ sigma, long long ms_stride, int ld_ms, float* __restrict__ lik,
+                        int Mtot, YT* __restrict__ yhat, int ld_yhat, float* __restrict__ yhat32, int ld32, int n,
+                        int HW, int nslices, int sw, int* __restrict__ sym, int* __restrict__ idx,
+                        const float* __restrict__ scale_table, int nscale, float bound, const int* __restrict__ q) {
+  __shared__ float qs[GCQ_TILE_MAX], ss[GCQ_TILE_MAX];
+  const int b = blockIdx.x / nslices, j = blockIdx.x - b * nslices;
+  const int ld = sw + 1, tot = HW * sw;
+  const float delta = tmae_qstep(q ? q[b] : 0);
+  // phase 1: NHWC order
+  for (int e = threadIdx.x; e < tot; e += 1024) {
+    const int pix = e / sw, c = e - pix * sw;
+    const int m = b * HW + pix, ch = yoff + j * sw + c;
+    const size_t ms = j * ms_stride + (size_t)m * ld_ms + c;
+    const GcqElem v = gcq_quantize(y[(size_t)m * ldy + ch], mu[ms], sigma[ms], delta, bound);
+    if (yhat) yhat[(size_t)m * ld_yhat + ch] = to_out<YT>(v.yhat);
+    if (yhat32) yhat32[(size_t)m * ld32 + ch] = v.yhat;
+    qs[pix * ld + c] = v.qi;
+    ss[pix * ld + c] = v.s;
+  }
+  __syncthreads();
+  // phase 2: pixel fastest
+  for (int e = threadIdx.x; e < tot; e += 1024) {
+    const int c = e / HW, pix = e - c * HW;
+    const float qi = qs[pix * ld + c], s = ss[pix * ld + c];
+    if (lik) lik[((size_t)b * Mtot + yoff + j * sw + c) * HW + pix] = gcq_likelihood(qi, s);
+    const size_t pos = (size_t)j * n * sw * HW + ((size_t)b * sw + c) * HW + pix;
+    sym[pos] = (int)qi;
+    idx[pos] = gcq_index(s, scale_table, nscale);
+  }
+}
+
+extern "C" int tmae_gc_slices_code_q(const float* y, int ldy, int yoff, const float* mu, const float* sigma,
+                                     long long ms_stride, int ld_ms, float* lik, int Mtot, void* yhat, int yhat_dtype,
+                                     int ld_yhat, float* yhat32, int ld32, int n, int HW, int nslices, int sw,
+                                     int* symbols, int* indexes, const float* scale_table, int nscale,
+                                     float scale_bound, const int* q, void* stream) {
+  TMAE_REQUIRE(y && mu && sigma && symbols && indexes && scale_table && nscale >= 1,
+               "tmae_gc_slices_code_q: y/mu/sigma/symbols/indexes/scale_table required");
+  TMAE_REQUIRE(n >= 0 && HW >= 0 && nslices >= 0 && sw >= 0, "tmae_gc_slices_code_q: negative extent");
+  const hipStream_t st = (hipStream_t)stream;
+  const int total = n * HW * nslices * sw;
+  if (total <= 0) return TMAE_OK;
+  if (HW * (sw + 1) <= GCQ_TILE_MAX) {
+    const dim3 tg(n * nslices);
+    if (yhat_dtype == TMAE_BF16)
+      hipLaunchKernelGGL(gcq_slices_tiled_kernel<bf16>, tg, dim3(1024), 0, st, y, ldy, yoff, mu, sigma, ms_stride,
+                         ld_ms, lik, Mtot, (bf16*)yhat, ld_yhat, yhat32, ld32, n, HW, nslices, sw, symbols, indexes,
+                         scale_table, nscale, scale_bound, q);
+    else
+      hipLaunchKernelGGL(gcq_slices_tiled_kernel<float>, tg, dim3(1024), 0, st, y, ldy, yoff, mu, sigma, ms_stride,
+                         ld_ms, lik, Mtot, (float*)yhat, ld_yhat, yhat32, ld32, n, HW, nslices, sw, symbols, indexes,
+                         scale_table, nscale, scale_bound, q);
+    TMAE_LAUNCH_CHECK("tmae_gc_slices_code_q");
+  }
+  const dim3 grid(ceil_div(total, 256));
+  if (yhat_dtype == TMAE_BF16)
+    hipLaunchKernelGGL(gcq_slices_kernel<bf16>, grid, dim3(256), 0, st, y, ldy, yoff, mu, sigma, ms_stride, ld_ms, lik,
+                       Mtot, (bf16*)yhat, ld_yhat, yhat32, ld32, n, HW, nslices, sw, total, symbols, indexes,
+                       scale_table, nscale, scale_bound, q);
+  else
+    hipLaunchKernelGGL(gcq_slices_kernel<float>, grid, dim3(256), 0, st, y, ldy, yoff, mu, sigma, ms_stride, ld_ms, lik,
+                       Mtot, (float*)yhat, ld_yhat, yhat32, ld32, n, HW, nslices, sw, total, symbols, indexes,
+                       scale_table, nscale, scale_bound, q);
+  TMAE_LAUNCH_CHECK("tmae_gc_slices_code_q");
+}
+
+__global__ void __launch_bounds__(256)
+gcq_indexes_kernel(const float* __restrict__ sigma, long long ms_stride, int ld_ms, int n, int HW, int nslices, int sw,
+                   const float* __restrict__ scale_table, int nscale, float bound, int* __restrict__ idx, int total,
+                   const int* __restrict__ q) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int per_pix = nslices * sw;
+  const int m = i / per_pix, r = i - m * per_pix;
+  const int j = r / sw, c = r - j * sw;
+  const int b = m / HW, pix = m - b * HW;
+  const float s = gcq_scale(sigma[j * ms_stride + (size_t)m * ld_ms + c], tmae_qstep(q ? q[b] : 0), bound);
+  idx[(size_t)j * n * sw * HW + ((size_t)b * sw + c) * HW + pix] = gcq_index(s, scale_table, nscale);
+}
+
+extern "C" int tmae_gc_indexes_q(const float* sigma, long long ms_stride, int ld_ms, int n, int HW, int nslices,
+                                 int sw, const float* scale_table, int nscale, float scale_bound, int* indexes,
+                                 const int* q, void* stream) {
+  TMAE_REQUIRE(sigma && scale_table && indexes && nscale >= 1, "tmae_gc_indexes_q: bad arguments");
+  TMAE_REQUIRE(n >= 0 && HW >= 0 && nslices >= 0 && sw >= 0, "tmae_gc_indexes_q: negative extent");
+  const int total = n * HW * nslices * sw;
+  if (total <= 0) return TMAE_OK;
+  hipLaunchKernelGGL(gcq_indexes_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, sigma,
+                     ms_stride, ld_ms, n, HW, nslices, sw, scale_table, nscale, scale_bound, indexes, total, q);
+  TMAE_LAUNCH_CHECK("tmae_gc_indexes_q");
+}
+
+template <typename YT>
+__global__ void __launch_bounds__(256)
+gcq_dequantize_kernel(const int* __restrict__ sym, const float* __restrict__ mu, long long ms_stride, int ld_ms, int n,
+                      int HW, int nslices, int sw, int yoff, YT* __restrict__ yhat, int ld_yhat,
+                      float* __restrict__ yhat32, int ld32, int total, const int* __restrict__ q) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int per_pix = nslices * sw;
+  const int m = i / per_pix, r = i - m * per_pix;
+  const int j = r / sw, c = r - j * sw;
+  const int b = m / HW, pix = m - b * HW;
+  const int ch = yoff + j * sw + c;
+  const float v = gcq_recon((float)sym[(size_t)j * n * sw * HW + ((size_t)b * sw + c) * HW + pix],
+                            mu[j * ms_stride + (size_t)m * ld_ms + c], tmae_qstep(q ? q[b] : 0));
+  yhat[(size_t)m * ld_yhat + ch] = to_out<YT>(v);
+  if (yhat32) yhat32[(size_t)m * ld32 + ch] = v;
+}
+
+extern "C" int tmae_gc_dequantize_q(const int* symbols, const float* mu, long long ms_stride, int ld_ms, int n, int HW,
+                                    int nslices, int sw, int yoff, void* yhat, int yhat_dtype, int ld_yhat,
+                                    float* yhat32, int ld32, const int* q, void* stream) {
+  TMAE_REQUIRE(symbols && mu && yhat, "tmae_gc_dequantize_q: bad arguments");
+  TMAE_REQUIRE(n >= 0 && HW >= 0 && nslices >= 0 && sw >= 0, "tmae_gc_dequantize_q: negative extent");
+  const int total = n * HW * nslices * sw;
+  if (total <= 0) return TMAE_OK;
+  const dim3 grid(ceil_div(total, 256));
+  if (yhat_dtype == TMAE_BF16)
+    hipLaunchKernelGGL(gcq_dequantize_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, symbols, mu, ms_stride,
+                       ld_ms, n, HW, nslices, sw, yoff, (bf16*)yhat, ld_yhat, yhat32, ld32, total, q);
+  else
+    hipLaunchKernelGGL(gcq_dequantize_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, symbols, mu, ms_stride,
+                       ld_ms, n, HW, nslices, sw, yoff, (float*)yhat, ld_yhat, yhat32, ld32, total, q);
+  TMAE_LAUNCH_CHECK("tmae_gc_dequantize_q");
+}
+
 // inv[b][p[b][j]] = j  (ids_shuffle = argsort(ids_restore) for a permutation, MCM.py:580)
 __global__ void invert_permutation_kernel(const int64_t* __restrict__ p, int64_t* __restrict__ inv, int L, int total) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -224,3 +224,16 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ---------------------------------------------------------------- quantiser step ladder
+// delta(q) = F[q mod 8] * 2^floor(q / 8) for q in -32..32 (1/16 .. 16, delta(0) = 1 exactly): F[k] is the f32
+// nearest to 2^(k/8), written out so that no libm is involved; the scaling by a power of two is exact.
+// bitstream.qstep is the Python mirror; both are pinned by tests/test_qstep_host.py.
+#define TMAE_Q_MIN (-32)
+#define TMAE_Q_MAX 32
+__host__ __device__ __forceinline__ float tmae_qstep(int q) {
+  constexpr float F[8] = {1.0f,        1.09050775f, 1.18920708f, 1.29683959f,
+                          1.41421354f, 1.54221082f, 1.68179286f, 1.8340081f};
+  q = q < TMAE_Q_MIN ? TMAE_Q_MIN : (q > TMAE_Q_MAX ? TMAE_Q_MAX : q);
+  return ldexpf(F[q & 7], q >> 3);  // two's complement: q & 7 = q mod 8, q >> 3 = floor(q / 8)
+}

@@ -353,7 +353,24 @@ class MCM(CompressionModel):
             ex = self._executor(len(strings[1]), dev)
             return {"x_hat": ex.decompress(strings, shape, ids_restore)}
 
-    def compress_batch(self, imgs, total_scores, lanes=1, z_lanes=None):
+    @staticmethod
+    def _check_q(q, B, who):
+        """q= of the batch methods -> None (no q, or every entry 0: the plain path) or a list of B ladder positions
+        (bitstream.check_q); an int stands for all B images.  ValueError before anything is launched"""
+        from .bitstream import check_q
+
+        if q is None:
+            return None
+        if np.ndim(q) == 0:
+            qs = [check_q(q, f"{who}: q")] * B
+        else:
+            qs = list(q.tolist() if hasattr(q, "tolist") else q)
+            if len(qs) != B:
+                raise ValueError(f"{who}: {len(qs)} entries of q for {B} images: one per image, or one int for all")
+            qs = [check_q(v, f"{who}: q[{b}]") for b, v in enumerate(qs)]
+        return qs if any(qs) else None
+
+    def compress_batch(self, imgs, total_scores, lanes=1, z_lanes=None, q=None):
         """compress with one independent record per image, coded on the device (csrc/rans_device.hip) ->
         {"string": [y_strings, z_strings], "shape", "ids_restore"}, len(y_strings) == len(z_strings) == B.
         Image b's (y_strings[b], z_strings[b]) are the strings MCM.compress (MCM.py:805-894) returns for that image
@@ -362,23 +379,30 @@ class MCM(CompressionModel):
         lanes / z_lanes (powers of two in 1..64, z_lanes=None: 1) deal an image's y / z symbols over that many
         interleaved rANS states, which shortens the serial chain of the coder; the strings are then the records of
         coder.encode_record, the result also carries "lanes": (lanes, z_lanes), and decompress_batch needs the same
-        values.  (1, 1) is the plain format above."""
+        values.  (1, 1) is the plain format above.
+
+        q: ladder positions of the y quantiser step, an int or a sequence of B ints in -32..32
+        (bitstream.qstep: step 2^(q/8), 1/16 .. 16); image b's y symbols are round((y - mu) / step_b) and its record
+        grows as q falls.  None, or all zero, is the path above with its kernels and bytes; decompress_batch needs
+        the same q.  z is not scaled."""
         from .coder import check_lanes
 
         lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
+        q = self._check_q(q, imgs.shape[0], "compress_batch")
         if not imgs.is_cuda:
             raise ValueError("MCM.compress_batch runs on the MI355X kernels: move the model and inputs to the GPU")
         self.entropy_bottleneck._check_cdf()
         self.gaussian_conditional._check_cdf()
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            return ex.compress_batch(imgs, total_scores, lanes, z_lanes)
+            return ex.compress_batch(imgs, total_scores, lanes, z_lanes, q)
 
-    def decompress_batch(self, strings, shape, ids_restore=None, lanes=1, z_lanes=None):
+    def decompress_batch(self, strings, shape, ids_restore=None, lanes=1, z_lanes=None, q=None):
         """inverse of compress_batch -> {"x_hat"}: strings = [y_strings, z_strings], one of each per image.  The
         streams are decoded on the device inside the slice loop; a corrupt stream raises ValueError naming its image
         after the whole batch has been enqueued.  lanes / z_lanes are compress_batch's; a record whose header does
-        not fit them raises ValueError naming its image before anything is launched."""
+        not fit them raises ValueError naming its image before anything is launched.  q: compress_batch's (an int or
+        one per image), checked before anything is launched as well."""
         from .coder import check_lanes
 
         lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
@@ -387,6 +411,7 @@ class MCM(CompressionModel):
             raise ValueError("MCM.decompress_batch needs ids_restore (the decoder unshuffles by it, MCM.py:667-669)")
         if len(strings[0]) != len(strings[1]):
             raise ValueError(f"{len(strings[0])} y strings but {len(strings[1])} z strings: one of each per image")
+        q = self._check_q(q, len(strings[1]), "decompress_batch")
         self.entropy_bottleneck._check_cdf()
         self.gaussian_conditional._check_cdf()
         dev = next(self.parameters()).device
@@ -394,42 +419,86 @@ class MCM(CompressionModel):
             raise ValueError("MCM.decompress_batch runs on the MI355X kernels: move the model to the GPU")
         with torch.no_grad():
             ex = self._executor(len(strings[1]), dev)
-            return {"x_hat": ex.decompress_batch(strings, shape, ids_restore, lanes, z_lanes)}
+            return {"x_hat": ex.decompress_batch(strings, shape, ids_restore, lanes, z_lanes, q=q)}
 
     def _geometry(self):
         """(img_size, patch_size, num_keep_patches, L) as the container header states them"""
         pe = self.encoder_embed
         return int(pe.img_size[0]), int(pe.patch_size[0]), int(self.num_keep_patches), int(pe.num_patches)
 
-    def encode_bytes(self, imgs, total_scores, lanes=1, z_lanes=None, orig_sizes=None):
+    def encode_bytes(self, imgs, total_scores, lanes=1, z_lanes=None, orig_sizes=None, q=None, target_bytes=None):
         """compress_batch into self-contained bitstreams -> list of B bytes objects (bitstream.py, container version
         1): header (geometry, lanes, original size), the kept patch ids packed on the device (ops.ids_pack, at
         ceil(log2 L) bits each), then compress_batch's z and y records of the image as they are.  decode_bytes needs
-        nothing else, in this process or another.  orig_sizes: optional list of B (width, height) to record."""
+        nothing else, in this process or another.  orig_sizes: optional list of B (width, height) to record.
+
+        q: compress_batch's (an int or B ints); an image coded at q != 0 becomes a TQC blob that records its q, one
+        at q = 0 the TMC blob as before.  target_bytes (an int or B ints) instead picks per image the smallest q of
+        the ladder whose whole blob (header, ids, z and y) is at most that many bytes: a lower-bound bisection over
+        -32..32 for all images at once, at most 7 probes, each of which repeats only the slice loop and the y coder
+        (the analysis up to h_s runs once).  The blob kept is the one of the image's smallest successful probe.  The
+        size is taken to be non-increasing in q; an image that does not fit at q = 32 gets its q = 32 blob, longer
+        than the target.  q together with target_bytes raises ValueError."""
         from . import bitstream
 
         B = imgs.shape[0]
         if orig_sizes is not None and len(orig_sizes) != B:
             raise ValueError(f"{len(orig_sizes)} original sizes for {B} images")
-        lanes, z_lanes, ids, z, y = self._encode_sections(imgs, total_scores, lanes, z_lanes)
-        img, patch, K, _ = self._geometry()
+        if q is not None and target_bytes is not None:
+            raise ValueError("encode_bytes: give q or target_bytes, not both")
+        img, patch, K, L = self._geometry()
+        if target_bytes is not None:
+            fixed = 4 * bitstream.id_words(L, K)
+            lanes, z_lanes, ids, z, y, qs = self._encode_sections_target(
+                imgs, total_scores, lanes, z_lanes, self._check_targets(target_bytes, B, "encode_bytes"),
+                lambda v: (bitstream.QHEADER_BYTES if v else bitstream.HEADER_BYTES) + fixed)
+        else:
+            qs = self._check_q(q, B, "encode_bytes") or [0] * B
+            lanes, z_lanes, ids, z, y = self._encode_sections(imgs, total_scores, lanes, z_lanes, qs)
         return [bitstream.assemble(img, K, patch, lanes, z_lanes, None if orig_sizes is None else orig_sizes[b],
-                                   ids[b], z[b], y[b]) for b in range(B)]
+                                   ids[b], z[b], y[b], qs[b]) for b in range(B)]
 
-    def _encode_sections(self, imgs, total_scores, lanes, z_lanes):
+    @staticmethod
+    def _check_targets(target_bytes, B, who):
+        if isinstance(target_bytes, (int, np.integer)):
+            return [int(target_bytes)] * B
+        t = [int(v) for v in target_bytes]
+        if len(t) != B:
+            raise ValueError(f"{who}: {len(t)} entries of target_bytes for {B} images: one per image, or one int")
+        return t
+
+    def _encode_sections(self, imgs, total_scores, lanes, z_lanes, q=None):
         """the sections of encode_bytes' blobs (and of encode_image's tiles) -> (lanes, z_lanes, id words uint32-
         compatible numpy [B, W], z records, y records): compress_batch, then the kept ids packed on the device"""
-        out = self.compress_batch(imgs, total_scores, lanes, z_lanes)
+        out = self.compress_batch(imgs, total_scores, lanes, z_lanes, q)
         lanes, z_lanes = out.get("lanes", (1, 1))
         ids = ops.ids_pack(self._exec.last_ids_shuffle, self._geometry()[2]).cpu().numpy()  # the one extra copy
         y, z = out["string"]
         return lanes, z_lanes, ids, z, y
 
-    def _decode_sections(self, ids, z, y, lanes, z_lanes, who):
+    def _encode_sections_target(self, imgs, total_scores, lanes, z_lanes, targets, fixed_bytes):
+        """_encode_sections with per image the smallest q whose blob fits targets[b] -> (..., y records, q per image);
+        fixed_bytes(q): the bytes of a blob at q besides its z and y records"""
+        from .coder import check_lanes
+
+        lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
+        if not imgs.is_cuda:
+            raise ValueError("MCM.encode_bytes runs on the MI355X kernels: move the model and inputs to the GPU")
+        self.entropy_bottleneck._check_cdf()
+        self.gaussian_conditional._check_cdf()
+        with torch.no_grad():
+            ex = self._executor(imgs.shape[0], imgs.device)
+            z, y, qs = ex.compress_batch_target(imgs, total_scores, lanes, z_lanes, targets, fixed_bytes)
+        ids = ops.ids_pack(self._exec.last_ids_shuffle, self._geometry()[2]).cpu().numpy()
+        return lanes, z_lanes, ids, z, y, qs
+
+    def _decode_sections(self, ids, z, y, lanes, z_lanes, who, q=None):
         """inverse of _encode_sections -> x_hat [B, 3, S, S]: the id words (B uint32 [W] rows) go up, ops.ids_unpack
         validates and completes them on the device, the records take the decompress_batch path and the ids status
-        words are read with the coder's.  who: the calling method's name for the error message"""
+        words are read with the coder's.  who: the calling method's name for the error message; q: the images' ladder
+        positions as their containers state them (None: all zero)"""
         _, _, K, L = self._geometry()
+        q = self._check_q(q, len(ids), who)
         self.entropy_bottleneck._check_cdf()
         self.gaussian_conditional._check_cdf()
         dev = next(self.parameters()).device
@@ -440,7 +509,8 @@ class MCM(CompressionModel):
         with torch.no_grad():
             ex = self._executor(len(ids), dev)
             _, rest, status = ops.ids_unpack(words, L, K)
-            return ex.decompress_batch(strings, torch.Size([ex.hz, ex.hz]), rest, lanes, z_lanes, ids_status=status)
+            return ex.decompress_batch(strings, torch.Size([ex.hz, ex.hz]), rest, lanes, z_lanes, ids_status=status,
+                                       q=q)
 
     def decode_bytes(self, blobs):
         """inverse of encode_bytes -> {"x_hat": [B, 3, S, S], "orig_sizes": [(width, height) or None per image]}.
@@ -449,7 +519,9 @@ class MCM(CompressionModel):
         naming the blob's index before anything is launched.  The id words then go up, ops.ids_unpack validates and
         completes them into ids_restore on the device, and the records take the decompress_batch path; the ids
         status words are read with the coder's after everything is enqueued, and an image whose side information is
-        corrupt (decoded harmlessly with the identity permutation) raises ValueError("side information of image b")."""
+        corrupt (decoded harmlessly with the identity permutation) raises ValueError("side information of image b").
+        Each blob states the quantiser step it was coded at (TMC: 1, TQC: its q); blobs of different
+        steps, plain ones among them, decode together in one call."""
         from . import bitstream
 
         blobs = list(blobs)
@@ -470,16 +542,22 @@ class MCM(CompressionModel):
                                  f"({parsed[0].lanes}, {parsed[0].z_lanes}): decode them in separate calls")
             parsed.append(p)
         x_hat = self._decode_sections([p.ids for p in parsed], [p.z for p in parsed], [p.y for p in parsed],
-                                      parsed[0].lanes, parsed[0].z_lanes, "decode_bytes")
+                                      parsed[0].lanes, parsed[0].z_lanes, "decode_bytes", [p.q for p in parsed])
         return {"x_hat": x_hat, "orig_sizes": [p.orig_size for p in parsed]}
 
-    def encode_image(self, rgb_u8, overlap=32, lanes=1, z_lanes=None, tile_batch=16):
+    def encode_image(self, rgb_u8, overlap=32, lanes=1, z_lanes=None, tile_batch=16, q=None, target_bytes=None):
         """an image at its own resolution -> one TMT file (bitstream.assemble_image).  rgb_u8: uint8
         [H, W, 3], numpy or tensor (a host image is uploaded once).  The image is cut into overlapping model-sized
         tiles (tiling.py; overlap 0..img_size // 2) and every chunk of tile_batch tiles (the last may be smaller)
         goes through ops.tile_cut_u8, scores.image_scores of the tiles' gray and the encode_bytes path, a batch of
         tiles being a batch of images; a tile's bytes in the file are the id / z / y sections of its encode_bytes
-        blob.  Same preconditions and ValueErrors as compress_batch."""
+        blob.  Same preconditions and ValueErrors as compress_batch.
+
+        q: one ladder position for every tile of the file (compress_batch's q as an int); q != 0 gives a TQT file
+        that records it, q = 0 or None the TMT file as before.  target_bytes instead picks the smallest q whose
+        whole file is at most that many bytes, by the lower-bound bisection of encode_bytes on the file size (at
+        most 7 probes); here every probe codes the image anew, analysis included, and an image that
+        does not fit at q = 32 gets its q = 32 file.  q together with target_bytes raises ValueError."""
         from . import bitstream, tiling
         from .coder import check_lanes
         from .scores import image_scores
@@ -497,19 +575,36 @@ class MCM(CompressionModel):
         if not 1 <= tile_batch < 1 << 16:
             raise ValueError(f"encode_image: tile_batch {tile_batch} outside 1..65535")
         lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
+        if q is not None and target_bytes is not None:
+            raise ValueError("encode_image: give q or target_bytes, not both")
+        q = 0 if q is None else bitstream.check_q(q, "encode_image: q")
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise ValueError("MCM.encode_image runs on the MI355X kernels: move the model to the GPU")
         x = x.to(dev).contiguous()
-        ids, zs, ys = [], [], []
-        for t0 in range(0, g.T, tile_batch):
-            tiles, gray = ops.tile_cut_u8(x, img, g.O, t0, min(tile_batch, g.T - t0))
-            _, _, i, z, y = self._encode_sections(tiles, image_scores(gray, img, patch), lanes, z_lanes)
-            ids.append(i)
-            zs += list(z)
-            ys += list(y)
-        return bitstream.assemble_image(img, K, patch, lanes, z_lanes, g.O, W, H, tile_batch, np.concatenate(ids),
-                                        zs, ys)
+
+        def code(qv):
+            ids, zs, ys = [], [], []
+            for t0 in range(0, g.T, tile_batch):
+                tiles, gray = ops.tile_cut_u8(x, img, g.O, t0, min(tile_batch, g.T - t0))
+                _, _, i, z, y = self._encode_sections(tiles, image_scores(gray, img, patch), lanes, z_lanes, qv)
+                ids.append(i)
+                zs += list(z)
+                ys += list(y)
+            return bitstream.assemble_image(img, K, patch, lanes, z_lanes, g.O, W, H, tile_batch, np.concatenate(ids),
+                                            zs, ys, qv)
+
+        if target_bytes is None:
+            return code(q)
+        target, lo, hi, best, last = int(target_bytes), bitstream.Q_MIN, bitstream.Q_MAX + 1, None, None
+        while lo < hi:  # the smallest q that fits; hi = Q_MAX + 1 stands for "none does" and is never probed
+            mid = (lo + hi) // 2
+            last = code(mid)
+            if len(last) <= target:
+                best, hi = last, mid
+            else:
+                lo = mid + 1
+        return last if best is None else best  # none fits: the last probe was q = 32
 
     def decode_image(self, blob, tile_batch=None, out="f32"):
         """inverse of encode_image -> f32 [3, H, W] (out="f32") or uint8 [H, W, 3] (out="u8", the f32 image through
@@ -537,7 +632,7 @@ class MCM(CompressionModel):
             t1 = min(t0 + n, T)
             try:
                 x_hat = self._decode_sections(p.ids[t0:t1], p.z[t0:t1], p.y[t0:t1], p.lanes, p.z_lanes,
-                                              "decode_image")
+                                              "decode_image", p.q)
             except ValueError as e:  # the batch path names the image of its call: that is tile t0 + b of the file
                 raise ValueError(re.sub(r"\bimage (\d+)", lambda m: f"tile {t0 + int(m.group(1))}", str(e), count=1)
                                  ) from None
@@ -562,8 +657,9 @@ class MCM(CompressionModel):
         [R, 3, h, w] or uint8 [R, h, w, 3], each window decode_region's.  srcs may hold the same object several
         times: per distinct source the union of the tiles its windows need is read and decoded once.  The tiles of
         all sources are batched together in chunks of tile_batch (sources coded with other lanes in batches of
-        their own) and one ops.tile_blend_crops produces all windows.  ValueErrors as decode_region, naming the
-        source by its first position in srcs; the sources of one call must agree in their overlap."""
+        their own, files of different quantiser steps in one batch) and one ops.tile_blend_crops produces all
+        windows.  ValueErrors as decode_region, naming the source by its first position in srcs; the sources of one
+        call must agree in their overlap."""
         srcs, origins = list(srcs), list(origins)
         if len(srcs) != len(origins):
             raise ValueError(f"decode_crops: {len(srcs)} sources but {len(origins)} origins: one of each per window")
@@ -630,7 +726,7 @@ class MCM(CompressionModel):
             part = [sections[j] for j in jobs[s0:s1]]
             try:
                 x_hat = self._decode_sections([a[0] for a in part], [a[1] for a in part], [a[2] for a in part],
-                                              lanes[0], lanes[1], who)
+                                              lanes[0], lanes[1], who, [index[k].q for k, _ in jobs[s0:s1]])
             except ValueError as e:  # the batch path names the image of its call: that is job s0 + b
 
                 def name(m, s0=s0):
@@ -967,11 +1063,24 @@ class _Executor:
         shuf = ops.invert_permutation(ids_restore.to(self.device))
         return self._back(shuf, m.encoder_embed.proj.in_channels)
 
-    def _analysis(self, imgs, scores):
+    def _q_dev(self, q):
+        """the per-image ladder positions on the device (int32 [B], one upload) or None for the plain kernels"""
+        if q is None:
+            return None
+        return torch.tensor(q, dtype=torch.int32).to(self.device)
+
+    def _analysis(self, imgs, scores, qd=None):
         """the eval forward's analysis path with symbol / index outputs -> (zsym [B][N][hz*hz], y sym and idx
-        [slice][image][channel][pixel], ids_restore), all on the device"""
+        [slice][image][channel][pixel], ids_restore), all on the device; qd: _q_dev's positions"""
+        zsym, rest = self._analysis_head(imgs, scores)
+        sym, idx = self._analysis_slices(qd)
+        return zsym, sym, idx, rest
+
+    def _analysis_head(self, imgs, scores):
+        """everything of _analysis that does not depend on the y quantiser step: encoder, g_a, h_a, z and h_s ->
+        (zsym, ids_restore)"""
         m, B = self.m, self.batch
-        N, S, hz, sw, HW = m.hyperprior_depth, m.num_slices, self.hz, self.sw, self.g * self.g
+        N, hz = m.hyperprior_depth, self.hz
         eb = m.entropy_bottleneck
         shuf, rest = self._front(self._check_imgs(imgs), scores)
         self.last_ids_shuffle = shuf  # encode_bytes packs its kept ids as the blobs' side information
@@ -979,34 +1088,81 @@ class _Executor:
         ops.eb_likelihood(eb, self.Z, B, N, hz * hz, lik=self.ZLIK, zhat=self.ZHAT, table=self.eb_table)
         zsym = ops.eb_symbols(eb, self.Z, B, N, hz * hz, table=self.eb_table)
         self._h_s()
+        return zsym, rest
+
+    def _analysis_slices(self, qd=None):
+        """the slice loop of _analysis on what _analysis_head left (Y32, the h_s outputs) -> (sym, idx); it may be
+        run again at another qd: nothing it reads is written by it"""
+        m, B = self.m, self.batch
+        S, sw, HW = m.num_slices, self.sw, self.g * self.g
         sym = torch.empty(S * B * sw * HW, dtype=torch.int32, device=self.device)
         idx = torch.empty_like(sym)
-        self._slices(self._gc_compress(sym, idx))
-        return zsym, sym, idx, rest
+        self._slices(self._gc_compress(sym, idx, qd))
+        return sym, idx
 
-    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1):
-        """compress with the device coder: the same symbol / index buffers, coded as one y and one z record per
-        image (image b's y stream = its [slice][channel][pixel] symbols) of lanes / z_lanes lanes
-        (coder.encode_record); one lane is the plain stream, the reference's batch-1 format B times"""
+    def _code_z(self, zsym, z_lanes):
+        m, B, hz = self.m, self.batch, self.hz
+        nz = m.hyperprior_depth * hz * hz
+        return self._encoder().encode_records(zsym, (0, nz), self._z_indexes(), (0, 0), B, 1, nz,
+                                              m.entropy_bottleneck.device_tables(), z_lanes, what="z stream of image")
+
+    def _code_y(self, sym, idx, lanes):
+        m, B, per = self.m, self.batch, self.sw * self.g * self.g
+        return self._encoder().encode_records(sym, (B * per, per), idx, (B * per, per), B, m.num_slices, per,
+                                              m.gaussian_conditional.device_tables(), lanes, what="y stream of image")
+
+    def _encoder(self):
         from .coder import DeviceRansEncoder
 
-        m, B = self.m, self.batch
-        N, S, hz, per = m.hyperprior_depth, m.num_slices, self.hz, self.sw * self.g * self.g
-        eb, gc = m.entropy_bottleneck, m.gaussian_conditional
-        zsym, sym, idx, rest = self._analysis(imgs, scores)
         enc = self.__dict__.get("_dev_encoder")
         if enc is None:
             enc = self._dev_encoder = DeviceRansEncoder()
-        nz = N * hz * hz
-        z_strings = enc.encode_records(zsym, (0, nz), self._z_indexes(), (0, 0), B, 1, nz, eb.device_tables(), z_lanes,
-                                       what="z stream of image")
-        y_strings = enc.encode_records(sym, (B * per, per), idx, (B * per, per), B, S, per, gc.device_tables(), lanes,
-                                       what="y stream of image")
+        return enc
+
+    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1, q=None):
+        """compress with the device coder: the same symbol / index buffers, coded as one y and one z record per
+        image (image b's y stream = its [slice][channel][pixel] symbols) of lanes / z_lanes lanes
+        (coder.encode_record); one lane is the plain stream, the reference's batch-1 format B times.  q: None or B
+        ladder positions, uploaded once before the first launch"""
+        hz = self.hz
+        zsym, sym, idx, rest = self._analysis(imgs, scores, self._q_dev(q))
+        z_strings = self._code_z(zsym, z_lanes)
+        y_strings = self._code_y(sym, idx, lanes)
         self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # rate diagnostics
         out = {"string": [y_strings, z_strings], "shape": torch.Size([hz, hz]), "ids_restore": rest}
         if lanes > 1 or z_lanes > 1:
             out["lanes"] = (lanes, z_lanes)
         return out
+
+    def compress_batch_target(self, imgs, scores, lanes, z_lanes, targets, fixed_bytes):
+        """compress_batch with per image the smallest q of the ladder at which fixed_bytes(q) + its z record + its y
+        record is at most targets[b] -> (z records, y records, q per image).  Lower-bound bisection over Q_MIN..Q_MAX
+        for all images at once (hi = Q_MAX + 1 stands for "no q fits" and is never probed): at most 7 probes, each the
+        slice loop and the y coder at the images' current midpoints; the analysis head and the z records are done
+        once.  An image's record is the one of its smallest successful probe; where none fits, of its last probe,
+        which is q = Q_MAX.  The size is taken to be non-increasing in q."""
+        from .bitstream import Q_MAX, Q_MIN
+
+        B = self.batch
+        zsym, rest = self._analysis_head(imgs, scores)
+        z_strings = self._code_z(zsym, z_lanes)
+        lo, hi = [Q_MIN] * B, [Q_MAX + 1] * B
+        kept = [None] * B  # (q, y record)
+        while any(l < h for l, h in zip(lo, hi)):
+            mid = [(l + h) // 2 if l < h else min(l, Q_MAX) for l, h in zip(lo, hi)]  # settled images: any valid q
+            sym, idx = self._analysis_slices(self._q_dev(mid))
+            y_strings = self._code_y(sym, idx, lanes)
+            for b in range(B):
+                if lo[b] >= hi[b]:
+                    continue
+                if fixed_bytes(mid[b]) + len(z_strings[b]) + len(y_strings[b]) <= targets[b]:
+                    hi[b], kept[b] = mid[b], (mid[b], y_strings[b])
+                else:
+                    lo[b] = mid[b] + 1
+                    if mid[b] == Q_MAX:
+                        kept[b] = (Q_MAX, y_strings[b])
+        self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # of the last probe
+        return z_strings, [k[1] for k in kept], [k[0] for k in kept]
 
     def _z_indexes(self):
         """EntropyBottleneck channel indexes of one image's z symbols [C][hz*hz] on the device (shared by all images)"""
@@ -1016,11 +1172,12 @@ class _Executor:
             zidx = self._zidx = torch.from_numpy(zidx).to(self.device)
         return zidx
 
-    def decompress_batch(self, strings, shape, ids_restore, lanes=1, z_lanes=1, ids_status=None):
+    def decompress_batch(self, strings, shape, ids_restore, lanes=1, z_lanes=1, ids_status=None, q=None):
         """decompress of per-image records: every string goes up in one copy, the z and y streams are decoded by
         device kernels (the y streams inside the slice loop, one call per slice step), and nothing synchronises with
         the host until the status words are read after the last kernel of _back has been enqueued.  ids_status
-        (decode_bytes): ops.ids_unpack's device status words of ids_restore, read in that same copy"""
+        (decode_bytes): ops.ids_unpack's device status words of ids_restore, read in that same copy.  q: None or B
+        ladder positions (compress_batch's), uploaded before the first launch"""
         from .bitstream import IDS_STATUS
         from .coder import DeviceRansDecoder, _raise_status
 
@@ -1034,6 +1191,7 @@ class _Executor:
         bound = float(gc.scale_bound) if gc.scale_bound is not None else 0.11
         zidx = self._z_indexes()
         rest = ids_restore.to(self.device)
+        qd = self._q_dev(q)
         dec = DeviceRansDecoder()  # records [0, B): y, [B, 2B): z; a bad header raises here, before the first launch
         dec.set_records(list(strings[0]) + list(strings[1]), [lanes] * B + [z_lanes] * B, self.device,
                         what=[f"{c} stream of image {b}" for c in "yz" for b in range(B)])
@@ -1048,12 +1206,20 @@ class _Executor:
         M, dt = m.latent_depth, self.dtype
 
         def step(i0, nbs, mu, sigma, ms_stride):
-            ops.gc_indexes(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:])
+            if qd is None:
+                ops.gc_indexes(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:])
+            else:
+                ops.gc_indexes_q(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:], qd)
             decode(0, B, idx, (per, sw * HW), sym, (per, sw * HW), i0, nbs, sw * HW, gtabs)
-            ops.gc_dequantize(sym[i0 * per:], mu, ms_stride, sw, B, HW, nbs, sw, i0 * sw, self.SUPY, dt, M, self.YPRE,
-                              M)
+            if qd is None:
+                ops.gc_dequantize(sym[i0 * per:], mu, ms_stride, sw, B, HW, nbs, sw, i0 * sw, self.SUPY, dt, M,
+                                  self.YPRE, M)
+            else:
+                ops.gc_dequantize_q(sym[i0 * per:], mu, ms_stride, sw, B, HW, nbs, sw, i0 * sw, self.SUPY, dt, M,
+                                    self.YPRE, M, qd)
 
         self._slices(step)
+        self.last_decoded = _LazyStreams(y_symbols=sym, y_indexes=idx)  # what the decoder saw (diagnostics, tests)
         shuf = ops.invert_permutation(rest)
         x_hat = self._back(shuf, m.encoder_embed.proj.in_channels)
         status = dec.status(ids_status)  # the only synchronisation: after everything is enqueued
@@ -1177,15 +1343,22 @@ class _Executor:
                           self.YPRE, M, B, HW, nbs, sw)
         return step
 
-    def _gc_compress(self, sym, idx):
-        """eval step + int32 symbols / scale indexes in the coder's [slice][image][channel][pixel] order"""
+    def _gc_compress(self, sym, idx, qd=None):
+        """eval step + int32 symbols / scale indexes in the coder's [slice][image][channel][pixel] order; qd: per-image
+        ladder positions on the device (the _q kernel, which skips the likelihoods nobody reads here) or None"""
+        gc = self.m.gaussian_conditional
         M, sw, B, HW, dt = self.m.latent_depth, self.sw, self.batch, self.g * self.g, self.dtype
-        table = self.m.gaussian_conditional.scale_table
+        table = gc.scale_table
+        bound = float(gc.scale_bound) if gc.scale_bound is not None else 0.11
         per = B * sw * HW
 
         def step(i0, nbs, mu, sigma, ms_stride):
-            ops.gc_slices_code(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, self.YLIK, M, self.SUPY, dt, M,
-                               self.YPRE, M, B, HW, nbs, sw, sym[i0 * per:], idx[i0 * per:], table)
+            if qd is None:
+                ops.gc_slices_code(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, self.YLIK, M, self.SUPY, dt, M,
+                                   self.YPRE, M, B, HW, nbs, sw, sym[i0 * per:], idx[i0 * per:], table)
+            else:
+                ops.gc_slices_code_q(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, None, M, self.SUPY, dt, M,
+                                     self.YPRE, M, B, HW, nbs, sw, sym[i0 * per:], idx[i0 * per:], table, bound, qd)
         return step
 
     def _gc_decompress(self, decoder):

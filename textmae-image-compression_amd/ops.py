@@ -19,7 +19,8 @@ __all__ = [
     "ids_shuffle", "layernorm", "linear", "linear_residual", "patch_embed", "cls_rows", "mha", "decoder_embed",
     "mask_rows", "decoder_pred", "conv3x3", "lic_stack", "pack_lic_stack_weight", "lic_stack_fits", "gc_slices", "eb_likelihood", "eb_aux_loss",
     "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "mha_plan", "mha_force_stream", "dtype_code", "gc_slices_code", "gc_indexes",
-    "gc_dequantize", "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
+    "gc_dequantize", "gc_slices_code_q", "gc_indexes_q", "gc_dequantize_q",
+    "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "rans_encode_lanes", "rans_decode_lanes", "ids_pack", "ids_unpack",
     "resize_tables", "resize_u8", "rgb_to_gray_u8", "tile_cut_u8", "tile_blend", "tile_blend_crops",
@@ -486,6 +487,38 @@ def gc_indexes(sigma, ms_stride, ld_ms, n, HW, nslices, sw, scale_table, scale_b
 def gc_dequantize(symbols, mu, ms_stride, ld_ms, n, HW, nslices, sw, yoff, yhat, yhat_dtype, ld_yhat, yhat32, ld32):
     _lib.call("tmae_gc_dequantize", _p(symbols), _p(mu), ms_stride, ld_ms, n, HW, nslices, sw, yoff, _p(yhat),
               dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, _stream())
+
+
+def _q_ptr(q, n):
+    """device address of the per-image ladder positions (int32 [n]) or None = all zero"""
+    if q is None:
+        return None
+    _need(q, torch.int32, "q")
+    if q.numel() != n:
+        raise ValueError(f"q holds {q.numel()} entries for {n} images")
+    return q.data_ptr()
+
+
+def gc_slices_code_q(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, lik, Mtot, yhat, yhat_dtype, ld_yhat, yhat32, ld32, n,
+                     HW, nslices, sw, symbols, indexes, scale_table, scale_bound, q):
+    """gc_slices_code at a per-image quantiser step: q int32 [n] on the device, ladder positions
+    in -32..32 (bitstream.qstep), or None = all zero; lik may be None"""
+    st = _need(scale_table.contiguous(), torch.float32, "scale_table")
+    _lib.call("tmae_gc_slices_code_q", _p(y), ldy, yoff, _p(mu), _p(sigma), ms_stride, ld_ms, _p(lik), Mtot, _p(yhat),
+              dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, n, HW, nslices, sw, _p(symbols), _p(indexes),
+              st.data_ptr(), st.numel(), float(scale_bound), _q_ptr(q, n), _stream())
+
+
+def gc_indexes_q(sigma, ms_stride, ld_ms, n, HW, nslices, sw, scale_table, scale_bound, indexes, q):
+    st = _need(scale_table.contiguous(), torch.float32, "scale_table")
+    _lib.call("tmae_gc_indexes_q", _p(sigma), ms_stride, ld_ms, n, HW, nslices, sw, st.data_ptr(), st.numel(),
+              float(scale_bound), _p(indexes), _q_ptr(q, n), _stream())
+
+
+def gc_dequantize_q(symbols, mu, ms_stride, ld_ms, n, HW, nslices, sw, yoff, yhat, yhat_dtype, ld_yhat, yhat32, ld32,
+                    q):
+    _lib.call("tmae_gc_dequantize_q", _p(symbols), _p(mu), ms_stride, ld_ms, n, HW, nslices, sw, yoff, _p(yhat),
+              dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, _q_ptr(q, n), _stream())
 
 
 def gc_pmf(scale_table, pmf_center, max_length):

@@ -114,10 +114,11 @@ def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None,
 
 @torch.no_grad()
 def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_dir, output_dir=None, lanes=None,
-                        original_size=False):
+                        original_size=False, q=None):
     """--bitstream DIR: encode_bytes -> DIR/<name>.tmc -> read the file back -> decode_bytes.  The bpp is that of
     the file, 8 * size / pixels: header and side information counted in full.  original_size takes the size the
-    blob itself recorded."""
+    blob itself recorded.  q (--q N): the y quantiser step's ladder position (MCM.encode_bytes), read back from the
+    file by decode_bytes."""
     device = next(model.parameters()).device
     x = x.to(device)
     total_score = total_score.to(device)
@@ -125,7 +126,7 @@ def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_d
     torch.cuda.synchronize()
     start = time.time()
     blobs = model.encode_bytes(x, total_score, lanes=1 if lanes is None else lanes,
-                               orig_sizes=[(int(ori_shape[0]), int(ori_shape[1]))])
+                               orig_sizes=[(int(ori_shape[0]), int(ori_shape[1]))], q=q)
     enc_time = time.time() - start
     with open(path, "wb") as f:
         f.write(blobs[0])
@@ -147,7 +148,8 @@ MS_SSIM_MIN_SIDE = 161  # five scales of an 11-tap window: the smaller side must
 
 
 @torch.no_grad()
-def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, output_dir=None, lanes=None, tile_batch=16):
+def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, output_dir=None, lanes=None, tile_batch=16,
+                    q=None):
     """--tiled: the image at its own resolution, rgb uint8 [H, W, 3] -> MCM.encode_image -> (with bitstream_dir)
     DIR/<name>.tmt, read back -> MCM.decode_image.  PSNR / MS-SSIM against the original pixels at that resolution,
     bpp = 8 * file size / (W * H).  An image too small for MS-SSIM's five scales gets PSNR only (no "ms-ssim")."""
@@ -158,7 +160,7 @@ def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, outpu
     H, W = int(x.shape[0]), int(x.shape[1])
     torch.cuda.synchronize()
     start = time.time()
-    blob = model.encode_image(x, overlap=overlap, lanes=1 if lanes is None else lanes, tile_batch=tile_batch)
+    blob = model.encode_image(x, overlap=overlap, lanes=1 if lanes is None else lanes, tile_batch=tile_batch, q=q)
     enc_time = time.time() - start
     if bitstream_dir is not None:
         path = os.path.join(bitstream_dir, Path(file_name).stem + ".tmt")
@@ -175,8 +177,8 @@ def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, outpu
     if min(H, W) >= MS_SSIM_MIN_SIDE:
         rv.update(compute_metrics(org, rec.unsqueeze(0), 255))
     else:  # compute_metrics' PSNR alone: both images rounded to 0..255
-        q = rec.mul(255).clamp(0, 255).round()
-        mse = float((org[0].mul(255).round() - q).square().mean())
+        r255 = rec.mul(255).clamp(0, 255).round()
+        mse = float((org[0].mul(255).round() - r255).square().mean())
         rv["psnr"] = 20.0 * math.log10(255.0) - 10.0 * math.log10(mse) if mse > 0 else float("inf")
     if output_dir is not None:
         from PIL import Image
@@ -186,7 +188,7 @@ def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, outpu
     return rv
 
 
-def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_dir=None, tile_batch=16):
+def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_dir=None, tile_batch=16, q=None):
     """--tiled counterpart of eval_model over image files: every metric averaged over the images that have it
     -> (metrics, number of images with MS-SSIM)"""
     from PIL import Image
@@ -197,7 +199,7 @@ def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_d
     sums, counts = defaultdict(float), defaultdict(int)
     for p in filepaths:
         rv = inference_tiled(model, np.array(Image.open(p).convert("RGB")), p.name, overlap, bitstream_dir, output_dir,
-                             lanes, tile_batch)
+                             lanes, tile_batch, q)
         for k, v in rv.items():
             sums[k] += v
             counts[k] += 1
@@ -241,7 +243,7 @@ def load_test_images(paths, size=224, device=None):
 
 
 def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False, lanes=None,
-               original_size=False, bitstream_dir=None):
+               original_size=False, bitstream_dir=None, q=None):
     """testing.py:128-165 over pre-loaded (img [1,3,S,S], orig_shape) pairs and a [N, L] score tensor; with
     bitstream_dir every image goes through its .tmc file there (inference_bitstream; needs names)"""
     metrics = defaultdict(float)
@@ -257,7 +259,7 @@ def eval_model(model, output_dir, images, scores, names=None, entropy_estimation
             rv = inference_entropy_estimation(model, img, ts)
         elif bitstream_dir is not None:
             rv = inference_bitstream(model, img, ori_shape, ts, names[i], bitstream_dir, output_dir, lanes=lanes,
-                                     original_size=original_size)
+                                     original_size=original_size, q=q)
         else:
             rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir, lanes=lanes,
                            original_size=original_size)
@@ -306,6 +308,9 @@ def setup_args():
                         "decode_image; with --bitstream DIR through DIR/<name>.tmt); metrics against the original "
                         "pixels, bpp = 8 * file size / (W * H)")
     p.add_argument("--overlap", type=int, default=32, help="tile overlap in pixels (--tiled)")
+    p.add_argument("--q", type=int, default=None, metavar="N",
+                   help="quantiser step 2^(N/8) on the y latents, N in -32..32 (--bitstream / --tiled; DESIGN.md "
+                        "§3.17): larger N, smaller files")
     return p
 
 
@@ -317,6 +322,9 @@ def main(argv):
         sys.exit(1)
     if args.tiled and args.entropy_estimation:
         print("Error: --tiled codes real files; it does not combine with --entropy-estimation.", file=sys.stderr)
+        sys.exit(1)
+    if args.q is not None and not (args.tiled or (args.bitstream is not None and not args.entropy_estimation)):
+        print("Error: --q codes real files: it needs --bitstream DIR or --tiled.", file=sys.stderr)
         sys.exit(1)
     if not args.tiled:
         ds = Path(args.dataset)
@@ -337,11 +345,11 @@ def main(argv):
         model.update(force=True)
         if args.tiled:
             m, with_msssim = eval_tiled(model, args.output_path, filepaths, args.overlap, lanes=args.lanes,
-                                        bitstream_dir=args.bitstream)
+                                        bitstream_dir=args.bitstream, q=args.q)
         else:
             m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths],
                            args.entropy_estimation, lanes=args.lanes, original_size=args.original_size,
-                           bitstream_dir=args.bitstream)
+                           bitstream_dir=args.bitstream, q=args.q)
         for k, v in m.items():
             results[k].append(v)
     desc = "entropy estimation" if args.entropy_estimation else args.entropy_coder
@@ -351,6 +359,8 @@ def main(argv):
                  f"{MS_SSIM_MIN_SIDE - 1}, PSNR only for the others")
     elif args.bitstream is not None and not args.entropy_estimation:
         desc += "; bpp of the .tmc files: header and side information counted in full"
+    if args.q:
+        desc += f"; y quantiser step 2^({args.q}/8)"
     output = {"name": "MCM", "description": f"Inference ({desc})", "results": results}
     print(json.dumps(output, indent=2))
     os.makedirs(args.output_path, exist_ok=True)

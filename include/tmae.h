@@ -197,6 +197,11 @@ typedef struct tmae_lic_stack_args {
    * racc[r] (rows rld[r] apart, +=; problem b1 at b1 * rs[r] elements) instead of GELU' and sv_act -- the
    * problems must not share an accumulator */
   float* racc[3]; int rld[3]; int rlim[3]; long long rs[3];
+  /* TMAE_LIC_STACK_CHAIN at a per-image quantiser step: device int32 [n] ladder positions, or NULL.
+   * The chain then builds y_hat_pre = fl(fl(rint((y - mu) / delta) delta) + mu), delta = delta(cq[image]), the
+   * arithmetic of tmae_gc_slices_fwd_q bit for bit (its own kernel instantiation: NULL runs the code it ran before
+   * the field existed).  Rejected with TMAE_LIC_STACK_BWD or without TMAE_LIC_STACK_CHAIN. */
+  const int* cq;
 } tmae_lic_stack_args;
 #define TMAE_LIC_STACK_CHAIN 1
 /* TMAE_LIC_STACK_BWD (training backward, mcm_train.py): the stack's data-gradient chain through LDS.  x1 = the
@@ -240,6 +245,17 @@ int tmae_lic_latent(const tmae_lic_latent_args* args, void* stream);
 int tmae_gc_slices_fwd(const float* y, int ldy, int yoff, const float* mu, const float* sigma, long long ms_stride,
                        int ld_ms, const float* noise, float* lik, int Mtot, void* yhat, int yhat_dtype, int ld_yhat,
                        float* yhat32, int ld32, int n, int HW, int nslices, int sw, void* stream);
+
+/* tmae_gc_slices_fwd at a per-image quantiser step on y (arithmetic of tmae_gc_slices_code_q below,
+ * every operation rounded to f32 on its own).  q: device int32 [n] ladder positions in -32..32 or NULL = all zero,
+ * delta = delta(q[image]); per element t = (y - mu) / delta, qi = rint(t),
+ *   yhat / yhat32 = fl(fl(qi delta) + mu), s = max(sigma / delta, scale_bound),
+ *   lik = max(Phi((0.5 - v) / s) - Phi((-0.5 - v) / s), 1e-9), v = |t + noise| with noise (training), |qi| without:
+ * the eval outputs are bitwise tmae_gc_slices_code_q's yhat, yhat32 and lik.  Layouts as tmae_gc_slices_fwd. */
+int tmae_gc_slices_fwd_q(const float* y, int ldy, int yoff, const float* mu, const float* sigma, long long ms_stride,
+                         int ld_ms, const float* noise, float* lik, int Mtot, void* yhat, int yhat_dtype, int ld_yhat,
+                         float* yhat32, int ld32, int n, int HW, int nslices, int sw, float scale_bound, const int* q,
+                         void* stream);
 
 /* compressai EntropyBottleneck parameters (filters = (3, 3, 3, 3)), all f32 device pointers */
 typedef struct tmae_eb_params {
@@ -656,6 +672,14 @@ int tmae_copy2d(const void* src, int lds, void* dst, int ldd, int rows, int cols
 int tmae_gc_bwd(const float* y, int ldy, int yoff, const float* mu, const float* sigma, int ld_ms, const float* noise,
                 int Mtot, const float* glik, const float* gyp, int ldg, float* dy, int lddy, void* dmu, void* dsigma,
                 int ldd, int n, int HW, int sw, int dtype, void* stream);
+/* The backward of tmae_gc_slices_fwd_q for one slice: q device int32 [n] or NULL, delta =
+ * delta(q[image]), t = (y - mu) / delta, s = max(sigma / delta, scale_bound), v = |t + noise| (training) or |rint(t)|.
+ * LowerBound semantics as above, the scale bound tested on sigma / delta; y_hat_pre straight-through (dy += gyp,
+ * nothing to mu); training: dy += sign(t + noise) g (phi_b - phi_a) / (s delta), dmu its negative; eval: the
+ * likelihood moves neither y nor mu; dsigma = g (b phi_b - a phi_a) / (s delta). */
+int tmae_gc_bwd_q(const float* y, int ldy, int yoff, const float* mu, const float* sigma, int ld_ms, const float* noise,
+                  int Mtot, const float* glik, const float* gyp, int ldg, float* dy, int lddy, void* dmu, void* dsigma,
+                  int ldd, int n, int HW, int sw, int dtype, float scale_bound, const int* q, void* stream);
 /* EntropyBottleneck likelihood backward (MCM.py:741-744): dz NHWC (= gzhat pass-through + likelihood path) and
  * every density parameter's gradient into `grads` (same struct, f32 gradient buffers; =/+=) */
 int tmae_eb_bwd(const tmae_eb_params* params, const float* z, const float* noise, const float* glik,

@@ -97,6 +97,7 @@ class LicStackArgs(ctypes.Structure):
         ("csv_pre", P * LSTK_MAXL), ("csv_act", P * LSTK_MAXL), ("cs_sv", LL * LSTK_MAXL),
         ("csv_t", P), ("cs_t", LL),
         ("racc", P * 3), ("rld", I * 3), ("rlim", I * 3), ("rs", LL * 3),
+        ("cq", P),
     ]
 
 
@@ -137,6 +138,7 @@ SIGNATURES = {
     "tmae_lic_stack": [ctypes.POINTER(LicStackArgs), P],
     "tmae_lic_latent": [ctypes.POINTER(LicLatentArgs), P],
     "tmae_gc_slices_fwd": [P, I, I, P, P, LL, I, P, P, I, P, I, I, P, I, I, I, I, I, P],
+    "tmae_gc_slices_fwd_q": [P, I, I, P, P, LL, I, P, P, I, P, I, I, P, I, I, I, I, I, F, P, P],
     "tmae_eb_likelihood_fwd": [P, ctypes.POINTER(EBParams), P, P, P, I, P, I, I, I, P],
     "tmae_eb_aux_loss": [ctypes.POINTER(EBParams), P, P, P, I, P],
     "tmae_gc_likelihood_fwd": [P, P, P, P, P, P, I, F, P],
@@ -217,6 +219,7 @@ SIGNATURES = {
     "tmae_lrp_bwd": [P, I, P, I, P, I, P, I, P, I, P, I, I, I, I, P],
     "tmae_copy2d": [P, I, P, I, I, I, I, P],
     "tmae_gc_bwd": [P, I, I, P, P, I, P, I, P, P, I, P, I, P, P, I, I, I, I, I, P],
+    "tmae_gc_bwd_q": [P, I, I, P, P, I, P, I, P, P, I, P, I, P, P, I, I, I, I, I, F, P, P],
     "tmae_eb_bwd": [ctypes.POINTER(EBParams), P, P, P, P, P, I, I, I, ctypes.POINTER(EBParams), I, P],
     "tmae_eb_aux_bwd": [ctypes.POINTER(EBParams), P, P, P, I, I, P],
     "tmae_bpp_bwd": [P, P, P, LL, ctypes.c_double, P],

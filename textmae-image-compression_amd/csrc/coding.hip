@@ -5,6 +5,7 @@
 // The symbol-emitting form of the slice likelihood kernel lives with it in conv.hip
 // (tmae_gc_slices_code); the EntropyBottleneck ones with its density tables in entropy.hip.
 #include "common.h"
+#include "gc_q.h"
 
 // GaussianConditional.update: pmf[i][j] = Phi((1/2 - s) / scale_i) - Phi((-1/2 - s) / scale_i),
 // s = |j - center_i|, Phi(x) = erfc(-x / sqrt 2) / 2; tail[i] = 2 Phi((-1/2 - center_i) / scale_i)
@@ -97,42 +98,13 @@ extern "C" int tmae_gc_dequantize(const int* symbols, const float* mu, long long
 }
 
 // ------------------------------------------------------------------ per-image quantiser step
-// The three kernels above with y quantised at a step delta(q[image]) of the ladder in common.h: symbols
-// rint((y - mu) / delta), reconstruction fl(fl(qi delta) + mu), entropy model at max(sigma / delta, bound).  The
-// reference has no counterpart.  Encoder and decoder must produce the same bits, and the tests restate the
-// arithmetic in numpy f32, so every operation is rounded on its own: the helpers are compiled with contraction off
-// (the __fmul_rn / __fadd_rn forms of the HIP headers are plain operators, which the default -ffp-contract=fast
-// may still fuse into one fma after inlining; the pragma is what keeps the product rounded).
-struct GcqElem { float qi, yhat, s; };
-
-__device__ __forceinline__ float gcq_recon(float qi, float mv, float delta) {
-#pragma clang fp contract(off)
-  const float p = qi * delta;
-  return p + mv;
-}
-
-__device__ __forceinline__ float gcq_scale(float sv, float delta, float bound) { return fmaxf(sv / delta, bound); }
-
-__device__ __forceinline__ GcqElem gcq_quantize(float yv, float mv, float sv, float delta, float bound) {
-#pragma clang fp contract(off)
-  const float d = yv - mv;
-  const float qi = rintf(d / delta);
-  return GcqElem{qi, gcq_recon(qi, mv, delta), gcq_scale(sv, delta, bound)};
-}
-
+// The three kernels above with y quantised at a step delta(q[image]) of the ladder in common.h.  The per-element
+// arithmetic (gcq_quantize / gcq_recon / gcq_scale / gcq_likelihood) is in gc_q.h, shared with the forward and the
+// backward at a step.
 __device__ __forceinline__ int gcq_index(float s, const float* __restrict__ scale_table, int nscale) {
   int id = nscale - 1;
   for (int t = 0; t < nscale - 1; ++t) id -= (s <= scale_table[t]) ? 1 : 0;
   return id;
-}
-
-// the symbol's probability mass under N(0, s): the table entry the coder approximates
-__device__ __forceinline__ float gcq_likelihood(float qi, float s) {
-  const float val = fabsf(qi);
-  const float k = -0.70710678118654752440f;
-  const float up = 0.5f * erfcf(k * ((0.5f - val) / s));
-  const float lo = 0.5f * erfcf(k * ((-0.5f - val) / s));
-  return fmaxf(up - lo, 1e-9f);
 }
 
 // one element per thread (maps past the LDS tile): gc_slices_kernel<YT, true>'s indexing
@@ -294,6 +266,94 @@ extern "C" int tmae_gc_dequantize_q(const int* symbols, const float* mu, long lo
     hipLaunchKernelGGL(gcq_dequantize_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, symbols, mu, ms_stride,
                        ld_ms, n, HW, nslices, sw, yoff, (float*)yhat, ld_yhat, yhat32, ld32, total, q);
   TMAE_LAUNCH_CHECK("tmae_gc_dequantize_q");
+}
+
+// ------------------------------------------------------------------ forward at a step
+// tmae_gc_slices_fwd (conv.hip) at delta(q[image]): y_hat = gcq_recon, s = gcq_scale, likelihood at |qi| (eval: bit
+// for bit tmae_gc_slices_code_q's) or at |t + noise| (training), t = (y - mu) / delta.  Both of its forms, same layouts.
+template <typename YT>
+__global__ void __launch_bounds__(256)
+gcq_fwd_kernel(const float* __restrict__ y, int ldy, int yoff, const float* __restrict__ mu,
+               const float* __restrict__ sigma, long long ms_stride, int ld_ms, const float* __restrict__ noise,
+               float* __restrict__ lik, int Mtot, YT* __restrict__ yhat, int ld_yhat, float* __restrict__ yhat32,
+               int ld32, int HW, int nslices, int sw, int total, float bound, const int* __restrict__ q) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int per_pix = nslices * sw;
+  const int m = i / per_pix, r = i - m * per_pix;
+  const int j = r / sw, c = r - j * sw;
+  const int ch = yoff + j * sw + c;
+  const int b = m / HW, pix = m - b * HW;
+  const float delta = tmae_qstep(q ? q[b] : 0);
+  const size_t ms = j * ms_stride + (size_t)m * ld_ms + c;
+  const float yv = y[(size_t)m * ldy + ch], mv = mu[ms];
+  const GcqElem e = gcq_quantize(yv, mv, sigma[ms], delta, bound);
+  if (yhat) yhat[(size_t)m * ld_yhat + ch] = to_out<YT>(e.yhat);
+  if (yhat32) yhat32[(size_t)m * ld32 + ch] = e.yhat;
+  const size_t nchw = ((size_t)b * Mtot + ch) * HW + pix;
+  lik[nchw] = noise ? gcq_likelihood_noisy(gcq_scaled(yv, mv, delta), noise[nchw], e.s) : gcq_likelihood(e.qi, e.s);
+}
+
+// one 1024-thread workgroup per (image, slice): gcq_slices_tiled_kernel's two phases; t goes through LDS (qi = rint(t))
+template <typename YT>
+__global__ void __launch_bounds__(1024)
+gcq_fwd_tiled_kernel(const float* __restrict__ y, int ldy, int yoff, const float* __restrict__ mu,
+                     const float* __restrict__ sigma, long long ms_stride, int ld_ms, const float* __restrict__ noise,
+                     float* __restrict__ lik, int Mtot, YT* __restrict__ yhat, int ld_yhat, float* __restrict__ yhat32,
+                     int ld32, int HW, int nslices, int sw, float bound, const int* __restrict__ q) {
+  __shared__ float ts[GCQ_TILE_MAX], ss[GCQ_TILE_MAX];
+  const int b = blockIdx.x / nslices, j = blockIdx.x - b * nslices;
+  const int ld = sw + 1, tot = HW * sw;
+  const float delta = tmae_qstep(q ? q[b] : 0);
+  // phase 1: NHWC order
+  for (int e = threadIdx.x; e < tot; e += 1024) {
+    const int pix = e / sw, c = e - pix * sw;
+    const int m = b * HW + pix, ch = yoff + j * sw + c;
+    const size_t ms = j * ms_stride + (size_t)m * ld_ms + c;
+    const float yv = y[(size_t)m * ldy + ch], mv = mu[ms];
+    const GcqElem v = gcq_quantize(yv, mv, sigma[ms], delta, bound);
+    if (yhat) yhat[(size_t)m * ld_yhat + ch] = to_out<YT>(v.yhat);
+    if (yhat32) yhat32[(size_t)m * ld32 + ch] = v.yhat;
+    ts[pix * ld + c] = gcq_scaled(yv, mv, delta);
+    ss[pix * ld + c] = v.s;
+  }
+  __syncthreads();
+  // phase 2: pixel fastest
+  for (int e = threadIdx.x; e < tot; e += 1024) {
+    const int c = e / HW, pix = e - c * HW;
+    const float t = ts[pix * ld + c], s = ss[pix * ld + c];
+    const size_t nchw = ((size_t)b * Mtot + yoff + j * sw + c) * HW + pix;
+    lik[nchw] = noise ? gcq_likelihood_noisy(t, noise[nchw], s) : gcq_likelihood(rintf(t), s);
+  }
+}
+
+extern "C" int tmae_gc_slices_fwd_q(const float* y, int ldy, int yoff, const float* mu, const float* sigma,
+                                    long long ms_stride, int ld_ms, const float* noise, float* lik, int Mtot,
+                                    void* yhat, int yhat_dtype, int ld_yhat, float* yhat32, int ld32, int n, int HW,
+                                    int nslices, int sw, float scale_bound, const int* q, void* stream) {
+  TMAE_REQUIRE(y && mu && sigma && lik, "tmae_gc_slices_fwd_q: y/mu/sigma/lik required");
+  TMAE_REQUIRE(n >= 0 && HW >= 0 && nslices >= 0 && sw >= 0, "tmae_gc_slices_fwd_q: negative extent");
+  const hipStream_t st = (hipStream_t)stream;
+  const int total = n * HW * nslices * sw;
+  if (total <= 0) return TMAE_OK;
+  if (HW * (sw + 1) <= GCQ_TILE_MAX) {
+    const dim3 tg(n * nslices);
+    if (yhat_dtype == TMAE_BF16)
+      hipLaunchKernelGGL(gcq_fwd_tiled_kernel<bf16>, tg, dim3(1024), 0, st, y, ldy, yoff, mu, sigma, ms_stride, ld_ms,
+                         noise, lik, Mtot, (bf16*)yhat, ld_yhat, yhat32, ld32, HW, nslices, sw, scale_bound, q);
+    else
+      hipLaunchKernelGGL(gcq_fwd_tiled_kernel<float>, tg, dim3(1024), 0, st, y, ldy, yoff, mu, sigma, ms_stride, ld_ms,
+                         noise, lik, Mtot, (float*)yhat, ld_yhat, yhat32, ld32, HW, nslices, sw, scale_bound, q);
+    TMAE_LAUNCH_CHECK("tmae_gc_slices_fwd_q");
+  }
+  const dim3 grid(ceil_div(total, 256));
+  if (yhat_dtype == TMAE_BF16)
+    hipLaunchKernelGGL(gcq_fwd_kernel<bf16>, grid, dim3(256), 0, st, y, ldy, yoff, mu, sigma, ms_stride, ld_ms, noise,
+                       lik, Mtot, (bf16*)yhat, ld_yhat, yhat32, ld32, HW, nslices, sw, total, scale_bound, q);
+  else
+    hipLaunchKernelGGL(gcq_fwd_kernel<float>, grid, dim3(256), 0, st, y, ldy, yoff, mu, sigma, ms_stride, ld_ms, noise,
+                       lik, Mtot, (float*)yhat, ld_yhat, yhat32, ld32, HW, nslices, sw, total, scale_bound, q);
+  TMAE_LAUNCH_CHECK("tmae_gc_slices_fwd_q");
 }
 
 // inv[b][p[b][j]] = j  (ids_shuffle = argsort(ids_restore) for a permutation, MCM.py:580)

@@ -12,6 +12,7 @@ Logging (MetricLogger / TensorBoard) is out of scope.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import distributed
@@ -40,10 +41,17 @@ METRICS = ("loss", "L1_loss", "ssim_loss", "vgg_loss", "bpp_loss", "aux_loss")
 
 
 def train_step(model, criterion, samples, total_scores, optimizer, aux_optimizer, clip_max_norm=1.0, accum_iter=1,
-               step_now=True, noise=None):
-    """one iteration of the reference loop body (utils/engine.py:72-91); returns the device losses"""
-    out_net = model(samples, total_scores, noise=noise) if noise is not None else model(samples, total_scores)
-    out_criterion = criterion(out_net, samples)
+               step_now=True, noise=None, q=None, lmbda=None):
+    """one iteration of the reference loop body (utils/engine.py:72-91); returns the device losses.  q: the y
+    quantiser step of this iteration (MCM.forward's q: an int, one per image, or an int32 device tensor), lmbda: the
+    criterion's weight for it (RateDistortionLoss.forward's lmbda, e.g. rd_loss.lmbda_for_q)"""
+    kw = {}
+    if noise is not None:
+        kw["noise"] = noise
+    if q is not None:
+        kw["q"] = q
+    out_net = model(samples, total_scores, **kw)
+    out_criterion = criterion(out_net, samples) if lmbda is None else criterion(out_net, samples, lmbda=lmbda)
     out_criterion["loss"] = out_criterion["loss"] / accum_iter
     aux_loss = model.aux_loss() / accum_iter
     if step_now:
@@ -90,10 +98,15 @@ class GraphedTrainStep:
     backward, so every replay runs them on the process group's stream under the remaining backward kernels, joined
     before clip / Adam (one ``graph.replay()`` per step at any world size, like the reference's one loop body,
     utils/engine.py:75-91).  The RCCL communicator exists before the capture (the eager warm-up step's
-    collectives).  A gloo group (host-staged all-reduce) is refused: use ``train_step`` there."""
+    collectives).  A gloo group (host-staged all-reduce) is refused: use ``train_step`` there.
+
+    q / lmbda, given at capture: the y quantiser step of the captured step (an int or one per
+    image) and the criterion's weight live in a static int32 [B] and a static 0-d f32 device buffer that every call
+    refreshes, so both may change from replay to replay without a new capture: the captured forward and backward
+    always run the kernels with a step, at q = 0 too."""
 
     def __init__(self, model, criterion, optimizer, aux_optimizer, samples, total_scores, clip_max_norm=1.0,
-                 warmup=1, noise=None):
+                 warmup=1, noise=None, q=None, lmbda=None):
         sync = getattr(model, "grad_sync", None)
         if sync is not None and not sync.capturable():
             raise ValueError("GraphedTrainStep: a gloo gradient all-reduce (host-staged) is not capturable; use "
@@ -107,6 +120,10 @@ class GraphedTrainStep:
         self.total_scores = total_scores.detach().clone()
         # injected quantisation noise (parity tests): static tensors refreshed per call like the batch
         self.noise = tuple(t.detach().clone() for t in noise) if noise is not None else None
+        dev = samples.device
+        self.q = None if q is None else torch.empty(samples.shape[0], dtype=torch.int32, device=dev)
+        self.lmbda = None if lmbda is None else torch.empty((), dtype=torch.float32, device=dev)
+        self._refresh_q(q, lmbda)
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.graph, self.out = None, None
         self._capture(warmup)
@@ -115,9 +132,31 @@ class GraphedTrainStep:
         return tuple((g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"])
                      for o in (self.optimizer, self.aux_optimizer) for g in o.param_groups)
 
+    def _refresh_q(self, q, lmbda):
+        """copy this call's q / lmbda into the static buffers (copy_ on the current stream, ahead of the replay)"""
+        if (q is None) != (self.q is None):
+            raise ValueError("GraphedTrainStep: q must be given at every call iff it was given at capture")
+        if (lmbda is None) != (self.lmbda is None):
+            raise ValueError("GraphedTrainStep: lmbda must be given at every call iff it was given at capture")
+        if q is not None:
+            if not (torch.is_tensor(q) and q.is_cuda):
+                from .mcm import MCM
+
+                qs = MCM._check_q(q, self.q.numel(), "GraphedTrainStep") or [0] * self.q.numel()
+                q = torch.tensor(qs, dtype=torch.int32)
+            elif q.dtype != torch.int32 or q.shape != self.q.shape:
+                raise ValueError(f"GraphedTrainStep: a device q must be int32 {tuple(self.q.shape)}, got {q.dtype} "
+                                 f"{tuple(q.shape)}")
+            self.q.copy_(q, non_blocking=True)
+        if lmbda is not None:
+            if torch.is_tensor(lmbda):
+                self.lmbda.copy_(lmbda.detach().reshape(()), non_blocking=True)
+            else:
+                self.lmbda.fill_(float(lmbda))
+
     def _step(self):
         return train_step(self.model, self.criterion, self.samples, self.total_scores, self.optimizer,
-                          self.aux_optimizer, self.clip_max_norm, noise=self.noise)
+                          self.aux_optimizer, self.clip_max_norm, noise=self.noise, q=self.q, lmbda=self.lmbda)
 
     def _capture(self, warmup):
         self.graph, self.out = None, None
@@ -152,11 +191,12 @@ class GraphedTrainStep:
         self.graph, self.out = g, out
         self._hyper_at_capture = self._hyper()
 
-    def __call__(self, samples, total_scores, noise=None):
+    def __call__(self, samples, total_scores, noise=None, q=None, lmbda=None):
         """one training step on (samples, total_scores); returns the step's device losses (static tensors,
         overwritten by the next call)"""
         if (noise is None) != (self.noise is None):
             raise ValueError("GraphedTrainStep: noise must be given at every call iff it was given at capture")
+        self._refresh_q(q, lmbda)
         if self._hyper() != self._hyper_at_capture:
             self._capture(0)
         self.samples.copy_(samples, non_blocking=True)
@@ -233,9 +273,33 @@ class GraphedMAEStep:
         return self.loss
 
 
+def q_schedule(q_range, q_seed, epoch):
+    """the seeded host generator train_one_epoch draws its per-step ladder positions from: next(gen) is uniform over
+    q_range = (lo, hi), both ends included; the same (q_seed, epoch) gives the same sequence"""
+    from .bitstream import check_q
+
+    lo, hi = (check_q(v, f"q_range[{i}]") for i, v in enumerate(q_range))
+    if lo > hi:
+        raise ValueError(f"q_range = {tuple(q_range)!r}: lo must not exceed hi")
+    rng = np.random.default_rng([int(q_seed), int(epoch)])
+
+    def draw():
+        while True:
+            yield int(rng.integers(lo, hi + 1))
+    return draw()  # the checks above run at the call, not at the first draw
+
+
 def train_one_epoch(model, criterion, train_dataloader, optimizer, aux_optimizer, epoch, clip_max_norm=1.0,
-                    accum_iter=1, log=None):
-    """utils/engine.py:30-156 (without MetricLogger / TensorBoard); returns the per-metric averages"""
+                    accum_iter=1, log=None, q_range=None, q_seed=0):
+    """utils/engine.py:30-156 (without MetricLogger / TensorBoard); returns the per-metric averages.
+
+    q_range = (lo, hi): every step draws one ladder position q from a host generator seeded with
+    (q_seed, epoch) and runs at the y quantiser step 2^(q/8) with the criterion's weight lmbda_for_q(criterion.lmbda,
+    q).  The whole batch shares the step's q: the distortion terms are batch means, so one weight per step is what the
+    loss can honour (per-image q stays available through model.forward / train_step)."""
+    from .rd_loss import lmbda_for_q
+
+    draw = q_schedule(q_range, q_seed, epoch) if q_range is not None else None
     model.train()
     device = next(model.parameters()).device
     optimizer.zero_grad()
@@ -245,8 +309,10 @@ def train_one_epoch(model, criterion, train_dataloader, optimizer, aux_optimizer
     for i, (samples, _ori_shape, total_scores) in enumerate(train_dataloader):
         samples = samples.to(device, non_blocking=True)
         total_scores = total_scores.to(device, non_blocking=True)
+        q = next(draw) if draw is not None else None
         out = train_step(model, criterion, samples, total_scores, optimizer, aux_optimizer, clip_max_norm, accum_iter,
-                         step_now=(i + 1) % accum_iter == 0)
+                         step_now=(i + 1) % accum_iter == 0, q=q,
+                         lmbda=None if q is None else lmbda_for_q(criterion.lmbda, q))
         vals = torch.stack([out[k].detach().float().reshape(()) for k in METRICS]).cpu().double()
         reduced = distributed.all_reduce_mean_many(vals.tolist())
         sums += torch.tensor(reduced, dtype=torch.float64)
@@ -257,8 +323,9 @@ def train_one_epoch(model, criterion, train_dataloader, optimizer, aux_optimizer
 
 
 @torch.no_grad()
-def val_one_epoch(epoch, val_dataloader, model, criterion):
-    """utils/engine.py:159-219: eval mode, no_grad, autocast (bf16 operands on MI355X)"""
+def val_one_epoch(epoch, val_dataloader, model, criterion, q=None):
+    """utils/engine.py:159-219: eval mode, no_grad, autocast (bf16 operands on MI355X).  q: the y quantiser step the
+    estimate is taken at (MCM.forward's q)"""
     model.eval()
     device = next(model.parameters()).device
     sums = torch.zeros(len(METRICS), dtype=torch.float64)
@@ -267,7 +334,7 @@ def val_one_epoch(epoch, val_dataloader, model, criterion):
         samples = samples.to(device)
         total_scores = total_scores.to(device)
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            out_net = model(samples, total_scores)
+            out_net = model(samples, total_scores) if q is None else model(samples, total_scores, q=q)
             out = criterion(out_net, samples)
             out["aux_loss"] = model.aux_loss()
         sums += torch.tensor([float(out[k]) for k in METRICS], dtype=torch.float64)

@@ -194,21 +194,40 @@ class MCM(CompressionModel):
         ex.refresh_weights()
         return ex
 
-    def forward(self, imgs, total_scores, noise=None):
+    def forward(self, imgs, total_scores, noise=None, q=None):
         """MCM.forward (MCM.py:714-803).  `noise=(z_noise, y_noise)` (NCHW, U(-1/2, 1/2)) replaces the
-        training-mode quantisation noise — used by parity tests; otherwise drawn on the device."""
+        training-mode quantisation noise — used by parity tests; otherwise drawn on the device.
+
+        q: ladder positions of the y quantiser step, as compress_batch takes them (an int or B ints
+        in -32..32), or an int32 [B] tensor on the device.  y is then quantised, reconstructed and modelled at the step
+        2^(q/8) with the coder's arithmetic: in eval x_hat is bitwise decompress_batch(compress_batch(q=), q=)'s and
+        the y likelihoods are the coded symbols' masses; under autograd the backward is that forward's.  None, or host
+        values that are all zero, is the path without q with its kernels and bits.  A device tensor is taken as given
+        (not read back, so the call can be captured into a graph) and always runs the kernels with a step."""
+        q = self._forward_q(q, imgs.shape[0])
         if not imgs.is_cuda:
             raise ValueError("MCM.forward runs on the MI355X kernels: move the model and inputs to the GPU")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return self._forward_train(imgs, total_scores, noise)
+            return self._forward_train(imgs, total_scores, noise, q)
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            out = ex.run(imgs, total_scores, self.training, noise)
+            out = ex.run(imgs, total_scores, self.training, noise, q=q)
             x_hat = out["x_hat"]
             loss = self.forward_loss(imgs, x_hat) if self.distortion != "none" else (ex.zero_loss,) * 3
         return {"loss": loss, "likelihoods": {"y": out["y"], "z": out["z"]}, "x_hat": x_hat}
 
-    def _forward_train(self, imgs, total_scores, noise):
+    @classmethod
+    def _forward_q(cls, q, B):
+        """q= of forward -> None, a list of B ladder positions (_check_q) or the caller's device tensor, checked for
+        what can be checked without reading it"""
+        if torch.is_tensor(q) and q.is_cuda:
+            if q.dtype != torch.int32 or q.dim() != 1 or q.numel() != B or not q.is_contiguous():
+                raise ValueError(f"forward: a device q must be a contiguous int32 [{B}] tensor, got {q.dtype} "
+                                 f"{tuple(q.shape)}")
+            return q
+        return cls._check_q(q, B, "forward")
+
+    def _forward_train(self, imgs, total_scores, noise, q=None):
         """MCM.forward under autograd (utils/engine.py:75): one autograd node whose forward keeps the
         activations and whose backward is the HIP reverse pass (mcm_train.py)."""
         from .mcm_train import TrainExec, _MCMTrainFn
@@ -220,7 +239,7 @@ class MCM(CompressionModel):
         ex = getattr(self, "_train_exec", None)
         if ex is None or ex.batch != B or ex.dtype != dt or ex.device != imgs.device:
             ex = self._train_exec = TrainExec(self, B, dt, imgs.device)
-        x_hat, ylik, zlik = _MCMTrainFn.apply(ex, noise, imgs, total_scores, *self.parameters())
+        x_hat, ylik, zlik = _MCMTrainFn.apply(ex, noise, q, imgs, total_scores, *self.parameters())
         loss = self.forward_loss(imgs, x_hat) if self.distortion != "none" else (
             torch.zeros((), device=imgs.device),) * 3
         return {"loss": loss, "likelihoods": {"y": ylik, "z": zlik}, "x_hat": x_hat}
@@ -810,6 +829,9 @@ class _Executor:
             raise ValueError(f"sqrt(num_keep_patches)={g} must be a multiple of 4 so h_s returns to the y grid")
         self.sw = M // S
         self.maxsup = S // 2
+        # the coder's scale bound, read once here: the forward at a quantiser step must not read the device back
+        gc = m.gaussian_conditional
+        self.scale_bound = float(gc.scale_bound) if gc.scale_bound is not None else 0.11
         self.nb = S - self.maxsup  # slices sharing the full support (batched)
         f32, dt = torch.float32, dtype
         dev = device
@@ -994,8 +1016,10 @@ class _Executor:
             raise ValueError(f"Input image size {tuple(imgs.shape[2:])} doesn't match model ({self.img})")
         return imgs
 
-    def run(self, imgs, scores, training, noise):
+    def run(self, imgs, scores, training, noise, q=None):
+        """q: None, B ladder positions (uploaded once, before the first launch) or an int32 [B] device tensor"""
         m, B = self.m, self.batch
+        qd = self._q_dev(q)
         M, N, g, hz = m.latent_depth, m.hyperprior_depth, self.g, self.hz
         imgs = self._check_imgs(imgs)
         if training:
@@ -1020,7 +1044,7 @@ class _Executor:
         self._h_s()
 
         # ---- slice loop (MCM.py:751-787)
-        self._slices(self._gc_forward(y_noise), chain_ok=True)
+        self._slices(self._gc_forward(y_noise, qd), chain_ok=True, cq=qd)
 
         x_hat = self._back(shuf, imgs.shape[1])
         return {"x_hat": x_hat, "y": self.YLIK, "z": self.ZLIK, "ids_restore": rest,
@@ -1065,8 +1089,8 @@ class _Executor:
 
     def _q_dev(self, q):
         """the per-image ladder positions on the device (int32 [B], one upload) or None for the plain kernels"""
-        if q is None:
-            return None
+        if q is None or torch.is_tensor(q):
+            return q
         return torch.tensor(q, dtype=torch.int32).to(self.device)
 
     def _analysis(self, imgs, scores, qd=None):
@@ -1335,12 +1359,18 @@ class _Executor:
     # Each is called with (i0, nbs, mu, sigma, ms_stride): slices i0..i0+nbs-1, mu/sigma device addresses
     # of rows [Mp][sw] per slice, ms_stride elements apart; it must leave y_hat (pre-LRP) in SUPY (operand
     # dtype) and YPRE (f32) at channels i0*sw.. .
-    def _gc_forward(self, y_noise):
+    def _gc_forward(self, y_noise, qd=None):
+        """qd: per-image ladder positions on the device (the kernel at a step) or None"""
         M, sw, B, HW, dt = self.m.latent_depth, self.sw, self.batch, self.g * self.g, self.dtype
+        bound = self.scale_bound
 
         def step(i0, nbs, mu, sigma, ms_stride):
-            ops.gc_slices(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, y_noise, self.YLIK, M, self.SUPY, dt, M,
-                          self.YPRE, M, B, HW, nbs, sw)
+            if qd is None:
+                ops.gc_slices(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, y_noise, self.YLIK, M, self.SUPY, dt, M,
+                              self.YPRE, M, B, HW, nbs, sw)
+            else:
+                ops.gc_slices_fwd_q(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, y_noise, self.YLIK, M, self.SUPY,
+                                    dt, M, self.YPRE, M, B, HW, nbs, sw, bound, qd)
         return step
 
     def _gc_compress(self, sym, idx, qd=None):
@@ -1398,7 +1428,7 @@ class _Executor:
                 cin = cout
             x, xs = out, out[0].numel()
 
-    def _slices(self, gc_step, chain_ok=False):
+    def _slices(self, gc_step, chain_ok=False, cq=None):
         m, dt, B, g = self.m, self.dtype, self.batch, self.g
         M, S, sw, ms, nb, Mp = m.latent_depth, m.num_slices, self.sw, self.maxsup, self.nb, self.Mp
         mid = self.mid
@@ -1551,7 +1581,7 @@ class _Executor:
             lb_ = [self.lrp_first[i][1]] + [b for _, b in self.lrp_layers[i]]
             ch = dict(w=lw, b=lb_, couts=mid, x1=supy, c1=sw * i, ld1=M, y=yv + i * sw * e4, ldy=M,
                       add=pbase + (off_lrp + i * c0) * eP, ld_add=Pw, ypre=ypre + i * sw * e4, ld_ypre=M,
-                      out=yh + i * sw * esz, ld_out=M, out2=supy + i * sw * esz, ld_out2=M)
+                      out=yh + i * sw * esz, ld_out=M, out2=supy + i * sw * esz, ld_out2=M, q=cq)
             ops.lic_stack(B, g, supy, sw * i, M, ws, bs_, mid, ms_ser + i * Mp * sw * e4, sw, True,
                           addend=pbase + (off_mean + i * c0) * eP, ld_add=Pw, nb=(2, 1), strides=st, chain=ch)
 

@@ -54,6 +54,10 @@ class TrainExec(_VitTrainBase):
         self.Mp = batch * K
         self.sw = m.latent_depth // m.num_slices
         self.ms = m.num_slices // 2
+        # the coder's scale bound of the step kernels, read once: a captured step must not read it back
+        gc = m.gaussian_conditional
+        self.scale_bound = float(gc.scale_bound) if gc.scale_bound is not None else 0.11
+        self.qd = None  # the forward's per-image ladder positions on the device, kept for its backward
         self.mid = [l.out_channels for l in _convs(m.cc_transform_mean[0])]
         S, ms = m.num_slices, self.ms
         self.cm, self.cs, self.cl = ([_convs(seq[i]) for i in range(S)]
@@ -113,9 +117,11 @@ class TrainExec(_VitTrainBase):
         return uniq
 
     # ------------------------------------------------------------------ forward
-    def forward(self, imgs, scores, noise):
+    def forward(self, imgs, scores, noise, q=None):
+        """q: None, B ladder positions (uploaded once, before the first launch) or an int32 [B] device tensor"""
         m, B, g = self.m, self.batch, self.g
         M, N, hz = m.latent_depth, m.hyperprior_depth, self.hz
+        self.qd = q if q is None or torch.is_tensor(q) else torch.tensor(q, dtype=torch.int32).to(self.device)
         imgs = self._begin(imgs)
         if noise is not None:
             self.z_noise, self.y_noise = (t.float().contiguous() for t in noise)
@@ -379,7 +385,7 @@ class TrainExec(_VitTrainBase):
             ch = dict(w=[w[0] for w in lw], b=[b[0] for b in lb], couts=mid, x1=lms + M * esz, c1=ny, ld1=2 * M,
                       y=self.Y32.data_ptr() + i * sw * e4, ldy=M, add=pb + (off_lrp + i * c0) * e4, ld_add=Pw,
                       ypre=self.YPRE.data_ptr() + i * sw * e4, ld_ypre=M, out=self.YH.data_ptr() + i * sw * esz,
-                      ld_out=M, out2=lms + (M + i * sw) * esz, ld_out2=2 * M)
+                      ld_out=M, out2=lms + (M + i * sw) * esz, ld_out2=2 * M, q=self.qd)
             save = {"layers": [(pre, act, (Mp * c, 0)) for (act, pre), c in zip(sv_ms, mid)],
                     "chain": [(pre, act, 0) for act, pre in sv_l], "chain_t": t}
             ops.lic_stack(B, g, lms + M * esz, ny, 2 * M, [w[0] for w in ws], [b[0] for b in bs], mid, MS[0, i], sw,
@@ -389,8 +395,7 @@ class TrainExec(_VitTrainBase):
                           "scale": [(a[1], p_[1]) for a, p_ in sv_ms] + [MS[1, i]],
                           "lrp": list(sv_l) + [t]}
         # Gaussian likelihoods + y_hat_pre (YPT, the backward's lrp input; YPRE) of the chained slices
-        ops.gc_slices(self.Y32, M, 0, MS[0], MS[1], Mp * sw, sw, self.y_noise, self.YLIK, M, self.YPT, dt, M,
-                      self.YPRE, M, B, HW, ms, sw)
+        self._gc_slices(0, MS[0], MS[1], ms)
         # ---- slices ms..S-1 batched on the support slots 0..ms-1
         i0, nbs = ms, S - ms
         bs_ = range(i0, S)
@@ -404,8 +409,7 @@ class TrainExec(_VitTrainBase):
         ops.lic_stack(B, g, lms + M * esz, sw * ms, 2 * M, [w[0] for w in ws], [b[0] for b in bsb], mid, MSB, sw, True,
                       addend=pb + (off_mean + i0 * c0) * e4, ld_add=Pw, nb=(2, nbs), strides=st,
                       save={"layers": [(pre, act, (nbs * Mp * c, Mp * c)) for (act, pre), c in zip(sv_b, mid)]})
-        ops.gc_slices(self.Y32, M, i0 * sw, MSB[0], MSB[1], Mp * sw, sw, self.y_noise, self.YLIK, M, self.YPT, dt, M,
-                      self.YPRE, M, B, HW, nbs, sw)
+        self._gc_slices(i0, MSB[0], MSB[1], nbs)
         lw, lb = stack_weights([cl[i] for i in bs_], M, sw * ms + sw)
         st = {"a": (0, c0), "y": (0, sw), "src": (0, sw), "x2": (0, sw)}
         for l in range(nl):
@@ -423,6 +427,24 @@ class TrainExec(_VitTrainBase):
             self.sl[i] = {"mean": [(a[0, j], p_[0, j]) for a, p_ in sv_b] + [MSB[0, j]],
                           "scale": [(a[1, j], p_[1, j]) for a, p_ in sv_b] + [MSB[1, j]],
                           "lrp": [(a[j], p_[j]) for a, p_ in sv_lb] + [tb[j]]}
+
+    def _gc_slices(self, i0, mu, sigma, nbs):
+        """GaussianConditional + quantize_ste of slices i0..i0+nbs-1 (mu / sigma blocks Mp * sw apart) -> YLIK, YPT,
+        YPRE; at the forward's quantiser step when it has one"""
+        M, sw, Mp, HW = self.m.latent_depth, self.sw, self.Mp, self.g * self.g
+        args = (self.Y32, M, i0 * sw, mu, sigma, Mp * sw, sw, self.y_noise, self.YLIK, M, self.YPT, self.dtype, M,
+                self.YPRE, M, self.batch, HW, nbs, sw)
+        if self.qd is None:
+            ops.gc_slices(*args)
+        else:
+            ops.gc_slices_fwd_q(*args, self.scale_bound, self.qd)
+
+    def _gc_bwd(self, *args):
+        """T.gc_bwd, at the forward's quantiser step when it had one"""
+        if self.qd is None:
+            T.gc_bwd(*args)
+        else:
+            T.gc_bwd_q(*args, self.scale_bound, self.qd)
 
     def _pack(self, stacks, l, kind, what="weight"):
         """layer l's `kind` copies of the weights (or what="bias") of `stacks` (conv lists: consecutive stacks of one
@@ -486,8 +508,7 @@ class TrainExec(_VitTrainBase):
                     recs[j]["mean"].append(mus[0, j])
                     recs[j]["scale"].append(mus[1, j])
         # GaussianConditional + quantize_ste of the nbs slices (mu / sigma blocks Mp * sw apart)
-        ops.gc_slices(self.Y32, M, i0 * sw, mus[0], mus[1], Mp * sw, sw, self.y_noise, self.YLIK, M, self.YPT, dt, M,
-                      self.YPRE, M, B, HW, nbs, sw)
+        self._gc_slices(i0, mus[0], mus[1], nbs)
         # lrp stacks: input [latent_means | slots 0..k-1] (shared) + this slice's y_hat_pre (x2, sw apart)
         x1, c1, ld1, x1s = self.LMS, M + sw * k, 2 * M, (0, 0)
         x2, c2, ld2, x2s = self.YPT.data_ptr() + i0 * sw * esz, sw, M, (0, sw)
@@ -747,8 +768,8 @@ class TrainExec(_VitTrainBase):
                               (self.LMS, cin_m, 2 * M, self.YPT.data_ptr() + i * sw * esz, sw, M),
                               [(dLM, M, M), (dSUP, M, sw * k), (gs_i, M, sw)])])
             # GaussianConditional + quantize_ste (MCM.py:771-776)
-            T.gc_bwd(self.Y32, M, i * sw, rec["mean"][-1], rec["scale"][-1], sw, self.y_noise, M, dylik, GS, M, DY, M,
-                     dMU, dSG, sw, B, HW, sw, dt)
+            self._gc_bwd(self.Y32, M, i * sw, rec["mean"][-1], rec["scale"][-1], sw, self.y_noise, M, dylik, GS, M, DY,
+                         M, dMU, dSG, sw, B, HW, sw, dt)
             scale = (self.cs[i], rec["scale"], dSG, (self.LS, M, 2 * M, lms + M * esz if k else None, sw * k, 2 * M),
                      [(dLS, M, M), (dSUP2, M, sw * k)])
             mean = (self.cm[i], rec["mean"], dMU, (self.LMS, cin_m, 2 * M, None, 0, 0),
@@ -819,8 +840,8 @@ class TrainExec(_VitTrainBase):
         # ---- GaussianConditional + quantize_ste per slice -> d mu, d sigma of every problem ([mean | scale][slice])
         dMS = self._e(2, nbs, Mp, sw)
         for j, i in enumerate(sl):
-            T.gc_bwd(self.Y32, M, i * sw, recs[j]["mean"][-1], recs[j]["scale"][-1], sw, self.y_noise, M, dylik, GS, M,
-                     DY, M, dMS[0, j], dMS[1, j], sw, B, HW, sw, dt)
+            self._gc_bwd(self.Y32, M, i * sw, recs[j]["mean"][-1], recs[j]["scale"][-1], sw, self.y_noise, M, dylik, GS,
+                         M, DY, M, dMS[0, j], dMS[1, j], sw, B, HW, sw, dt)
         dms, _ = self._stacks_bwd([(c[j], recs[j][key], dMS[t, j]) for t, (c, key) in enumerate(((cm, "mean"),
                                                                                                 (cs, "scale")))
                                    for j in range(nbs)], groups=2)
@@ -964,8 +985,8 @@ class _MCMTrainFn(torch.autograd.Function):
     """MCM.forward as one autograd node: (imgs, scores, *params) -> (x_hat, y likelihood, z likelihood)"""
 
     @staticmethod
-    def forward(ctx, ex, noise, imgs, scores, *params):
-        x_hat, ylik, zlik = ex.forward(imgs, scores, noise)
+    def forward(ctx, ex, noise, q, imgs, scores, *params):
+        x_hat, ylik, zlik = ex.forward(imgs, scores, noise, q)
         ctx.ex = ex
         ctx.params = params
         return x_hat, ylik, zlik
@@ -989,7 +1010,7 @@ class _MCMTrainFn(torch.autograd.Function):
             else:
                 off = ex.offsets[id(p)]
                 out.append(gflat[off:off + p.numel()].view(p.shape))
-        return (None, None, None, None, *out)
+        return (None, None, None, None, None, *out)
 
 
 # ---------------------------------------------------------------------- forward_encoder / forward_decoder alone

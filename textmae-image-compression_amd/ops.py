@@ -19,7 +19,7 @@ __all__ = [
     "ids_shuffle", "layernorm", "linear", "linear_residual", "patch_embed", "cls_rows", "mha", "decoder_embed",
     "mask_rows", "decoder_pred", "conv3x3", "lic_stack", "pack_lic_stack_weight", "lic_stack_fits", "gc_slices", "eb_likelihood", "eb_aux_loss",
     "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "mha_plan", "mha_force_stream", "dtype_code", "gc_slices_code", "gc_indexes",
-    "gc_dequantize", "gc_slices_code_q", "gc_indexes_q", "gc_dequantize_q",
+    "gc_dequantize", "gc_slices_fwd_q", "gc_slices_code_q", "gc_indexes_q", "gc_dequantize_q",
     "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "rans_encode_lanes", "rans_decode_lanes", "ids_pack", "ids_unpack",
@@ -409,6 +409,7 @@ def lic_stack(n, G, x1, c1, ld1, weights, biases, couts, y, ldy, y_f32, x2=None,
         a.csrc, a.cld_src = _p(chain["ypre"]), chain["ld_ypre"]
         a.cy, a.cldy = _p(chain["out"]), chain["ld_out"]
         a.cy2, a.cldy2 = _p(chain.get("out2")), chain.get("ld_out2", 0)
+        a.cq = _q_ptr(chain.get("q"), n)  # per-image quantiser step of y_hat_pre or None
         cs = chain.get("strides", {})  # per-slice (b2) element strides of the chain operands
         a.cs_x1, a.cs_yv, a.cs_src = cs.get("x1", 0), cs.get("y", 0), cs.get("ypre", 0)
         a.cs_add, a.cs_y, a.cs_y2 = cs.get("add", 0), cs.get("out", 0), cs.get("out2", 0)
@@ -507,6 +508,16 @@ def gc_slices_code_q(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, lik, Mtot, yhat,
     _lib.call("tmae_gc_slices_code_q", _p(y), ldy, yoff, _p(mu), _p(sigma), ms_stride, ld_ms, _p(lik), Mtot, _p(yhat),
               dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, n, HW, nslices, sw, _p(symbols), _p(indexes),
               st.data_ptr(), st.numel(), float(scale_bound), _q_ptr(q, n), _stream())
+
+
+def gc_slices_fwd_q(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, noise, lik, Mtot, yhat, yhat_dtype, ld_yhat, yhat32, ld32,
+                    n, HW, nslices, sw, scale_bound, q):
+    """gc_slices at a per-image quantiser step: q int32 [n] on the device or None = all zero; without
+    noise the outputs are bitwise gc_slices_code_q's y_hat and likelihood, with noise the training likelihood at
+    |(y - mu) / step + noise|"""
+    _lib.call("tmae_gc_slices_fwd_q", _p(y), ldy, yoff, _p(mu), _p(sigma), ms_stride, ld_ms, _p(noise), _p(lik), Mtot,
+              _p(yhat), dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, n, HW, nslices, sw, float(scale_bound),
+              _q_ptr(q, n), _stream())
 
 
 def gc_indexes_q(sigma, ms_stride, ld_ms, n, HW, nslices, sw, scale_table, scale_bound, indexes, q):

@@ -207,13 +207,14 @@ def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_d
 
 
 @torch.no_grad()
-def inference_entropy_estimation(model, x, total_score):
-    """testing.py:103-120 with the scores passed (the reference omits them and raises)"""
+def inference_entropy_estimation(model, x, total_score, q=None):
+    """testing.py:103-120 with the scores passed (the reference omits them and raises).  q (--q N): the estimate at
+    the y quantiser step 2^(N/8) (MCM.forward's q)"""
     device = next(model.parameters()).device
     x, total_score = x.to(device), total_score.to(device)
     torch.cuda.synchronize()
     start = time.time()
-    out = model.forward(x, total_score)
+    out = model.forward(x, total_score) if q is None else model.forward(x, total_score, q=q)
     torch.cuda.synchronize()
     elapsed = time.time() - start
     metrics = compute_metrics(x, out["x_hat"], 255)
@@ -256,7 +257,7 @@ def eval_model(model, output_dir, images, scores, names=None, entropy_estimation
     for i, (img, ori_shape) in enumerate(images):
         ts = scores[i:i + 1]
         if entropy_estimation:
-            rv = inference_entropy_estimation(model, img, ts)
+            rv = inference_entropy_estimation(model, img, ts, q=q)
         elif bitstream_dir is not None:
             rv = inference_bitstream(model, img, ori_shape, ts, names[i], bitstream_dir, output_dir, lanes=lanes,
                                      original_size=original_size, q=q)
@@ -309,8 +310,9 @@ def setup_args():
                         "pixels, bpp = 8 * file size / (W * H)")
     p.add_argument("--overlap", type=int, default=32, help="tile overlap in pixels (--tiled)")
     p.add_argument("--q", type=int, default=None, metavar="N",
-                   help="quantiser step 2^(N/8) on the y latents, N in -32..32 (--bitstream / --tiled; DESIGN.md "
-                        "§3.17): larger N, smaller files")
+                   help="quantiser step 2^(N/8) on the y latents, N in -32..32 (--bitstream / --tiled: DESIGN.md "
+                        "§3.17; --entropy-estimation: the estimated rate and x_hat at that step, §3.18): larger N, "
+                        "smaller files")
     return p
 
 
@@ -323,8 +325,9 @@ def main(argv):
     if args.tiled and args.entropy_estimation:
         print("Error: --tiled codes real files; it does not combine with --entropy-estimation.", file=sys.stderr)
         sys.exit(1)
-    if args.q is not None and not (args.tiled or (args.bitstream is not None and not args.entropy_estimation)):
-        print("Error: --q codes real files: it needs --bitstream DIR or --tiled.", file=sys.stderr)
+    if args.q is not None and not (args.tiled or args.bitstream is not None or args.entropy_estimation):
+        print("Error: --q needs --bitstream DIR or --tiled (real files) or --entropy-estimation (the estimate).",
+              file=sys.stderr)
         sys.exit(1)
     if not args.tiled:
         ds = Path(args.dataset)

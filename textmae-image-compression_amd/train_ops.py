@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDgradArgs, WgradArgs
-from .ops import _p, _stream, dtype_code
+from .ops import _p, _q_ptr, _stream, dtype_code
 
 _SCRATCH: dict = {}
 
@@ -209,6 +209,15 @@ def lrp_bwd(t, ldt, dt, lddt, rows, C, dtype, g32=None, ld32=0, g16=None, ld16=0
             ld32b=0):
     _lib.call("tmae_lrp_bwd", _p(g32), ld32, _p(g32b), ld32b, _p(g16), ld16, _p(t), ldt, _p(dt), lddt, _p(gsum), ldgs,
               rows, C, dtype_code(dtype), _stream())
+
+
+def gc_bwd_q(y, ldy, yoff, mu, sigma, ld_ms, noise, Mtot, glik, gyp, ldg, dy, lddy, dmu, dsigma, ldd, n, HW, sw, dtype,
+             scale_bound, q):
+    """gc_bwd at a per-image quantiser step: the backward of ops.gc_slices_fwd_q; q int32 [n] on
+    the device or None = all zero"""
+    _lib.call("tmae_gc_bwd_q", _p(y), ldy, yoff, _p(mu), _p(sigma), ld_ms, _p(noise), Mtot, _p(glik), _p(gyp), ldg,
+              _p(dy), lddy, _p(dmu), _p(dsigma), ldd, n, HW, sw, dtype_code(dtype), float(scale_bound),
+              _q_ptr(q, n), _stream())
 
 
 def gc_bwd(y, ldy, yoff, mu, sigma, ld_ms, noise, Mtot, glik, gyp, ldg, dy, lddy, dmu, dsigma, ldd, n, HW, sw, dtype):

@@ -351,6 +351,26 @@ int tmae_gc_dequantize_q(const int* symbols, const float* mu, long long ms_strid
                          int nslices, int sw, int yoff, void* yhat, int yhat_dtype, int ld_yhat, float* yhat32,
                          int ld32, const int* q, void* stream);
 
+/* The four kernels at a step with the step per pixel of the latent grid, i.e. per kept patch (g_a is
+ * 1x1 convolutions, so pixel p of the grid is kept token p).  qmap: device int32 [n][HW], required, the clamped ladder
+ * positions tmae_qmap_build writes; the element at (image b, pixel p, any channel) is quantised at delta(qmap[b][p])
+ * with the arithmetic above.  Signatures, layouts and both launch forms are those of the _q namesakes; the LDS form is
+ * bitwise the element form, and with qmap[b][.] = q[b] every output is bitwise the _q kernel's. */
+int tmae_gc_slices_code_qm(const float* y, int ldy, int yoff, const float* mu, const float* sigma, long long ms_stride,
+                           int ld_ms, float* lik, int Mtot, void* yhat, int yhat_dtype, int ld_yhat, float* yhat32,
+                           int ld32, int n, int HW, int nslices, int sw, int* symbols, int* indexes,
+                           const float* scale_table, int nscale, float scale_bound, const int* qmap, void* stream);
+int tmae_gc_indexes_qm(const float* sigma, long long ms_stride, int ld_ms, int n, int HW, int nslices, int sw,
+                       const float* scale_table, int nscale, float scale_bound, int* indexes, const int* qmap,
+                       void* stream);
+int tmae_gc_dequantize_qm(const int* symbols, const float* mu, long long ms_stride, int ld_ms, int n, int HW,
+                          int nslices, int sw, int yoff, void* yhat, int yhat_dtype, int ld_yhat, float* yhat32,
+                          int ld32, const int* qmap, void* stream);
+int tmae_gc_slices_fwd_qm(const float* y, int ldy, int yoff, const float* mu, const float* sigma, long long ms_stride,
+                          int ld_ms, const float* noise, float* lik, int Mtot, void* yhat, int yhat_dtype, int ld_yhat,
+                          float* yhat32, int ld32, int n, int HW, int nslices, int sw, float scale_bound,
+                          const int* qmap, void* stream);
+
 /* GaussianConditional.update (update_scale_table): pmf[n][max_length], tail[n] for the CDF builder */
 int tmae_gc_pmf(const float* scale_table, const int* pmf_center, int n, int max_length, float* pmf, float* tail,
                 void* stream);
@@ -378,6 +398,28 @@ int tmae_ids_pack(const int64_t* ids_shuffle, uint32_t* words, int n, int L, int
  * status gets the identity permutation in both outputs, so nothing downstream can index outside its rows. */
 int tmae_ids_unpack(const uint32_t* words, int64_t* ids_shuffle, int64_t* ids_restore, int* status, int n, int L,
                     int K, void* stream);
+
+/* ---- side information of the per-patch quantiser steps (csrc/qlevels.hip; DESIGN.md §3.19, bitstream.py) ----
+ * Per kept patch p a level l[p] in 0..nlev-1 (2 <= nlev <= 16) into the image's table of ladder offsets;
+ * 1 <= K <= L <= 1024.
+ * select: levels [n][K] from scores f32 [n][L] (s[p] = scores[b][ids_shuffle[b][p]], rank r[p] = #{p' : s[p'] > s[p] or
+ * (s[p'] == s[p] and p' < p)}, l[p] = r[p] nlev / K: level 0 is the highest-scoring share) or from a level map int32
+ * [n][L] in image patch order (l[p] = map[b][ids_shuffle[b][p]]); exactly one of the two non-NULL.  status [n]: 0 ok,
+ * 1 a map entry outside 0..nlev-1, and then all-zero levels for that image. */
+int tmae_qlevels_select(const float* scores, const int* map, const int64_t* ids_shuffle, int* levels, int* status,
+                        int n, int L, int K, int nlev, void* stream);
+/* pack: levels [n][K] -> words [n][W2], W2 = ceil(K lbits / 32), lbits = max(1, ceil(log2 nlev)); tmae_ids_pack's bit
+ * order (LSB first, tail bits zero). */
+int tmae_qlevels_pack(const int* levels, uint32_t* words, int n, int K, int nlev, void* stream);
+/* unpack: words [n][ldw] (rows padded to a common ldw by the host) with a table size per image, nlev int32 [n] on the
+ * device -> levels [n][K], status [n]: 0 ok, 1 a level >= nlev (or nlev outside 1..16, or the image's W2 > ldw),
+ * 2 non-zero tail bits, the lowest that applies; an image with a fault gets all-zero levels.  nlev[b] == 1: no map, no
+ * word is read, all levels 0. */
+int tmae_qlevels_unpack(const uint32_t* words, int ldw, const int* nlev, int* levels, int* status, int n, int K,
+                        void* stream);
+/* build: qmap[b][p] = clamp(q[b] + offsets[b][levels[b][p]], -32, 32); q int32 [n] or NULL (all zero), offsets int32
+ * [n][16]. */
+int tmae_qmap_build(const int* levels, const int* q, const int* offsets, int* qmap, int n, int K, void* stream);
 
 /* ---------------------------------------------------------------- entropy coding (host, no device work)
  * compressai 1.2.4's coder restated (csrc/rans.cpp; not vendored in the reference): 64-bit rANS, 16-bit

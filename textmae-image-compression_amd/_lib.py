@@ -157,6 +157,11 @@ SIGNATURES = {
     "tmae_gc_slices_code_q": [P, I, I, P, P, LL, I, P, I, P, I, I, P, I, I, I, I, I, P, P, P, I, F, P, P],
     "tmae_gc_indexes_q": [P, LL, I, I, I, I, I, P, I, F, P, P, P],
     "tmae_gc_dequantize_q": [P, P, LL, I, I, I, I, I, I, P, I, I, P, I, P, P],
+    # the four at a step per pixel of the latent grid (per kept patch; csrc/coding_qmap.hip)
+    "tmae_gc_slices_code_qm": [P, I, I, P, P, LL, I, P, I, P, I, I, P, I, I, I, I, I, P, P, P, I, F, P, P],
+    "tmae_gc_indexes_qm": [P, LL, I, I, I, I, I, P, I, F, P, P, P],
+    "tmae_gc_dequantize_qm": [P, P, LL, I, I, I, I, I, I, P, I, I, P, I, P, P],
+    "tmae_gc_slices_fwd_qm": [P, I, I, P, P, LL, I, P, P, I, P, I, I, P, I, I, I, I, I, F, P, P],
     "tmae_gc_pmf": [P, P, I, I, P, P, P],
     "tmae_eb_pmf": [ctypes.POINTER(EBParams), P, P, I, I, P, P, P],
     "tmae_eb_symbols": [P, ctypes.POINTER(EBParams), P, I, I, I, P, P],
@@ -165,6 +170,11 @@ SIGNATURES = {
     # side information of the per-image bitstream (csrc/ids_pack.hip)
     "tmae_ids_pack": [P, P, I, I, I, P],
     "tmae_ids_unpack": [P, P, P, P, I, I, I, P],
+    # side information of the per-patch quantiser steps (csrc/qlevels.hip)
+    "tmae_qlevels_select": [P, P, P, P, P, I, I, I, I, P],
+    "tmae_qlevels_pack": [P, P, I, I, I, P],
+    "tmae_qlevels_unpack": [P, I, P, P, P, I, I, P],
+    "tmae_qmap_build": [P, P, P, P, I, I, P],
     "tmae_pmf_to_quantized_cdf": [P, I, I, P],
     "tmae_rans_encoder_create": [ctypes.POINTER(ctypes.c_void_p)],
     "tmae_rans_encode_with_indexes": [P, P, P, LL, P, I, P, P, I],

@@ -29,6 +29,12 @@ touching the other tiles (``MCM.decode_region`` / ``decode_crops``, DESIGN.md §
 Blobs and files whose y latents were coded at a quantiser step other than 1 (``q=`` of the model's methods, DESIGN.md
 §3.17) carry the magics b"TQC" / b"TQT" and the ladder position q; every reader here takes both kinds and returns q
 as the last field of its tuple (0 for TMC / TMT).  ``qstep`` is the ladder.
+
+Blobs and files coded with a quantiser step per kept patch (``qoffsets=``) carry the magics b"TPC" /
+b"TPT": a base position q, a table of nlev ladder offsets and per kept patch a level into that table, packed like the
+ids.  The readers return them as trailing fields (nlev, offsets, level words), nlev = 1 and no level words for the other
+magics.  ``select_levels_host`` / ``pack_levels_host`` / ``unpack_levels_host`` / ``build_qmap_host`` at the end restate
+the kernels of csrc/qlevels.hip in numpy.
 """
 from __future__ import annotations
 
@@ -47,6 +53,14 @@ QHEADER_BYTES = 20
 Q_MIN, Q_MAX = -32, 32
 # F[k] = the f32 nearest to 2^(k/8), the literals of tmae_qstep (csrc/common.h)
 QSTEP_F = (1.0, 1.09050775, 1.18920708, 1.29683959, 1.41421354, 1.54221082, 1.68179286, 1.8340081)
+# the same blob with a quantiser step per kept patch: the 16 TMC header bytes; one word holding the
+# base position q as int8 (0 allowed), the table size nlev (2..16) and two zero bytes; 16 bytes of int8 ladder offsets
+# (-64..64, entries at index >= nlev zero); the id words; W2 = level_words(K, nlev) level words (level of kept patch k
+# at bits [k * lbits, (k + 1) * lbits), lbits = level_bits(nlev), the ids' bit order); then z and y as in TMC.
+PMAGIC = b"TPC"
+PHEADER_BYTES = 36
+NLEV_MIN, NLEV_MAX = 2, 16
+OFFSET_MIN, OFFSET_MAX = -64, 64
 MAX_L = 1024       # IDS_MAXL of the kernels
 MAX_LANE_LOG2 = 6  # lanes <= 64 (coder.check_lanes)
 _HEADER = struct.Struct("<3sBHHBBHHH")
@@ -80,6 +94,58 @@ def _read_q(byte, what, plain):
     return q
 
 
+# status words of tmae_qlevels_unpack / tmae_qlevels_select
+LEVELS_STATUS = {1: "quantiser level outside its table", 2: "non-zero padding bits of the level section"}
+
+
+def level_bits(nlev: int) -> int:
+    """bits of one packed level: max(1, ceil(log2 nlev))"""
+    return max(1, (int(nlev) - 1).bit_length())
+
+
+def level_words(K: int, nlev: int) -> int:
+    """32-bit words of the level section: ceil(K * lbits / 32); none for nlev = 1 (no map)"""
+    return 0 if int(nlev) < 2 else (int(K) * level_bits(nlev) + 31) // 32
+
+
+def check_offsets(offsets, who="qoffsets") -> tuple:
+    """the table of ladder offsets as a tuple of nlev ints: 2..16 integers in -64..64, ValueError otherwise"""
+    try:
+        offs = list(offsets.tolist() if hasattr(offsets, "tolist") else offsets)
+    except TypeError:
+        raise ValueError(f"{who} = {offsets!r}: a sequence of {NLEV_MIN}..{NLEV_MAX} integers") from None
+    if not NLEV_MIN <= len(offs) <= NLEV_MAX:
+        raise ValueError(f"{who}: nlev = {len(offs)} outside {NLEV_MIN}..{NLEV_MAX} (the entries of the offset table)")
+    out = []
+    for i, o in enumerate(offs):
+        v = int(o)
+        if v != o or not OFFSET_MIN <= v <= OFFSET_MAX:
+            raise ValueError(f"{who}[{i}] = {o!r}: offset outside {OFFSET_MIN}..{OFFSET_MAX} (integers)")
+        out.append(v)
+    return tuple(out)
+
+
+def _offset_bytes(offsets) -> bytes:
+    """the 16 int8 bytes of the offset table, entries past nlev zero"""
+    return struct.pack("<16b", *(tuple(offsets) + (0,) * (NLEV_MAX - len(offsets))))
+
+
+def _read_table(qbyte, nlev, table, what):
+    """q, nlev and the 16 offset bytes of a TPC / TPT header -> (q, offsets tuple of nlev ints)"""
+    q = qbyte - 256 if qbyte >= 128 else qbyte
+    if not Q_MIN <= q <= Q_MAX:
+        raise ValueError(f"{what} stream with q = {q}: the ladder is {Q_MIN}..{Q_MAX}")
+    if not NLEV_MIN <= nlev <= NLEV_MAX:
+        raise ValueError(f"{what} stream with nlev = {nlev}: outside {NLEV_MIN}..{NLEV_MAX}")
+    offs = struct.unpack("<16b", bytes(table))
+    for i, o in enumerate(offs[:nlev]):
+        if not OFFSET_MIN <= o <= OFFSET_MAX:
+            raise ValueError(f"{what} stream: offset {i} = {o} outside {OFFSET_MIN}..{OFFSET_MAX}")
+    if any(offs[nlev:]):
+        raise ValueError(f"{what} stream: unused offsets {offs[nlev:]} past nlev = {nlev} must be zero")
+    return q, offs[:nlev]
+
+
 class Blob(NamedTuple):
     """parse()'s result: the header fields, then views of the three sections"""
     img_size: int
@@ -91,7 +157,10 @@ class Blob(NamedTuple):
     ids: np.ndarray          # uint32 [W] view
     z: memoryview
     y: memoryview
-    q: int = 0               # ladder position of the y quantiser step (0: a TMC blob, else a TQC one)
+    q: int = 0               # ladder position of the y quantiser step (0: a TMC blob, else a TQC one; TPC: the base)
+    nlev: int = 1            # TPC: entries of the offset table (1: no map, the other magics)
+    offsets: tuple = ()      # TPC: the nlev ladder offsets
+    levels: np.ndarray | None = None  # TPC: uint32 [W2] view of the level words
 
     @property
     def num_patches(self) -> int:
@@ -126,10 +195,13 @@ def _check_geometry(img_size, K, patch):
     return L
 
 
-def pack_header(img_size, num_keep_patches, patch_size, lanes=1, z_lanes=1, z_words=0, orig_size=None, q=0) -> bytes:
-    """the 16 header bytes (q = 0, TMC) or the 20 of a TQC blob; z_words = length of the z record in 32-bit words,
-    orig_size = (width, height) or None"""
+def pack_header(img_size, num_keep_patches, patch_size, lanes=1, z_lanes=1, z_words=0, orig_size=None, q=0,
+                offsets=None) -> bytes:
+    """the 16 header bytes (q = 0, TMC), the 20 of a TQC blob or, with a table of offsets, the 36 of a TPC blob;
+    z_words = length of the z record in 32-bit words, orig_size = (width, height) or None"""
     q = check_q(q)
+    if offsets is not None:
+        offsets = check_offsets(offsets, "offsets")
     img_size, K, patch, z_words = int(img_size), int(num_keep_patches), int(patch_size), int(z_words)
     if not (0 < img_size < 1 << 16 and 0 < patch < 1 << 8):
         raise ValueError(f"img_size {img_size} / patch_size {patch} do not fit the header (u16 / u8)")
@@ -140,15 +212,20 @@ def pack_header(img_size, num_keep_patches, patch_size, lanes=1, z_lanes=1, z_wo
     if not (0 <= w < 1 << 16 and 0 <= h < 1 << 16):
         raise ValueError(f"original size {(w, h)} does not fit the header's u16 fields")
     nib = _log2_lanes(lanes, "lanes") | _log2_lanes(z_lanes, "z_lanes") << 4
+    if offsets is not None:
+        return _HEADER.pack(PMAGIC, VERSION, img_size, K, patch, nib, z_words, w, h) \
+            + struct.pack("<bBxx", q, len(offsets)) + _offset_bytes(offsets)
     if q:
         return _HEADER.pack(QMAGIC, VERSION, img_size, K, patch, nib, z_words, w, h) + struct.pack("<bxxx", q)
     return _HEADER.pack(MAGIC, VERSION, img_size, K, patch, nib, z_words, w, h)
 
 
 def assemble(img_size, num_keep_patches, patch_size, lanes, z_lanes, orig_size, ids_words, z_record, y_record,
-             q=0) -> bytes:
+             q=0, offsets=None, level_words_=None) -> bytes:
     """one blob from its parts; ids_words: uint32-compatible [W] array (pack_ids_host / ops.ids_pack of one image);
-    q: the ladder position the y record was coded at (0: a TMC blob, byte for byte; else TQC)"""
+    q: the ladder position the y record was coded at (0: a TMC blob, byte for byte; else TQC).  offsets (2..16 ints)
+    and level_words_ (uint32-compatible [W2], pack_levels_host / ops.qlevels_pack of the image): a TPC blob, q its
+    base position"""
     L = _check_geometry(int(img_size), int(num_keep_patches), int(patch_size))
     ids = np.ascontiguousarray(ids_words).view(np.uint32).reshape(-1).astype("<u4", copy=False)
     if ids.size != id_words(L, num_keep_patches):
@@ -156,19 +233,28 @@ def assemble(img_size, num_keep_patches, patch_size, lanes, z_lanes, orig_size, 
     z, y = bytes(z_record), bytes(y_record)
     if len(z) % 4 or len(y) % 4:
         raise ValueError(f"records are whole 32-bit words (z {len(z)} bytes, y {len(y)} bytes)")
-    return pack_header(img_size, num_keep_patches, patch_size, lanes, z_lanes, len(z) // 4, orig_size, q) \
-        + ids.tobytes() + z + y
+    lev = b""
+    if (offsets is None) != (level_words_ is None):
+        raise ValueError("assemble: offsets and level words go together")
+    if offsets is not None:
+        offsets = check_offsets(offsets, "offsets")
+        lv = np.ascontiguousarray(level_words_).view(np.uint32).reshape(-1).astype("<u4", copy=False)
+        if lv.size != level_words(num_keep_patches, len(offsets)):
+            raise ValueError(f"{lv.size} level words, {level_words(num_keep_patches, len(offsets))} expected")
+        lev = lv.tobytes()
+    return pack_header(img_size, num_keep_patches, patch_size, lanes, z_lanes, len(z) // 4, orig_size, q, offsets) \
+        + ids.tobytes() + lev + z + y
 
 
 def parse(blob) -> Blob:
     """header fields and views of the id words, the z record and the y record; ValueError on a blob that is not a
-    well-formed version-1 TMC or TQC container (the records themselves are checked by the coder)"""
+    well-formed version-1 TMC, TQC or TPC container (the records themselves are checked by the coder)"""
     mv = memoryview(blob).cast("B") if not isinstance(blob, memoryview) else blob.cast("B")
     n = len(mv)
     if n < HEADER_BYTES:
         raise ValueError(f"{n} bytes: shorter than the {HEADER_BYTES}-byte header")
     magic, version, img_size, K, patch, nib, z_words, w, h = _HEADER.unpack_from(mv, 0)
-    if magic not in (MAGIC, QMAGIC):
+    if magic not in (MAGIC, QMAGIC, PMAGIC):
         raise ValueError(f"not a TMC bitstream (magic {bytes(magic)!r})")
     if version != VERSION:
         raise ValueError(f"container version {version}, this reader knows version {VERSION}")
@@ -182,19 +268,30 @@ def parse(blob) -> Blob:
         q = _read_q(mv[16], "TQC", "TMC")
         if mv[17] or mv[18] or mv[19]:
             raise ValueError(f"TQC stream: padding bytes 17-19 hold {bytes(mv[17:20]).hex()}, must be zero")
+    nlev, offsets = 1, ()
+    if magic == PMAGIC:
+        hb = PHEADER_BYTES
+        if n < hb:
+            raise ValueError(f"{n} bytes: shorter than the {hb}-byte TPC header")
+        if mv[18] or mv[19]:
+            raise ValueError(f"TPC stream: padding bytes 18-19 hold {bytes(mv[18:20]).hex()}, must be zero")
+        q, offsets = _read_table(mv[16], mv[17], mv[20:36], "TPC")
+        nlev = len(offsets)
     ll, zl = nib & 15, nib >> 4
     if ll > MAX_LANE_LOG2 or zl > MAX_LANE_LOG2:
         raise ValueError(f"lane fields 2^{ll} / 2^{zl}: at most 2^{MAX_LANE_LOG2} lanes")
     L = _check_geometry(img_size, K, patch)
-    W = id_words(L, K)
-    need = hb + 4 * (W + z_words + 2)
+    W, W2 = id_words(L, K), level_words(K, nlev)
+    need = hb + 4 * (W + W2 + z_words + 2)
     if n < need:
-        raise ValueError(f"{n} bytes: header + {W} id words + {z_words} z words + at least 2 y words take {need}")
-    z0 = hb + 4 * W
+        raise ValueError(f"{n} bytes: header + {W} id words + " + (f"{W2} level words + " if nlev > 1 else "")
+                         + f"{z_words} z words + at least 2 y words take {need}")
+    z0 = hb + 4 * (W + W2)
     y0 = z0 + 4 * z_words
     ids = np.frombuffer(mv, dtype="<u4", count=W, offset=hb)
+    levels = np.frombuffer(mv, dtype="<u4", count=W2, offset=hb + 4 * W) if nlev > 1 else None
     return Blob(img_size, K, patch, 1 << ll, 1 << zl, (w, h) if (w, h) != (0, 0) else None, ids, mv[z0:y0], mv[y0:],
-                q)
+                q, nlev, offsets, levels)
 
 
 # ------------------------------------------------------------------------------------ tiled images: b"TMT", version 1
@@ -213,8 +310,15 @@ def parse(blob) -> Blob:
 #
 # b"TQT", version 1: the same file coded at one quantiser step other than 1: byte 18 holds the ladder
 # position q as int8, byte 19 stays zero, everything else as above.  q = 0 is always TMT.
+#
+# b"TPT", version 1: the file coded with a quantiser step per kept patch: byte 18 holds the base
+# position q as int8 (0 allowed), byte 19 the table size nlev (2..16); 16 bytes of int8 ladder offsets follow the 24
+# header bytes (entries at index >= nlev zero), then the table; per tile the id words, W2 = level_words(K, nlev) level
+# words, the z record and the y record.  One table of offsets per file, one level section per tile.
 IMAGE_MAGIC = b"TMT"
 IMAGE_QMAGIC = b"TQT"
+IMAGE_PMAGIC = b"TPT"
+IMAGE_PHEADER_BYTES = 40
 IMAGE_VERSION = 1
 IMAGE_HEADER_BYTES = 24
 _IMAGE_HEADER = struct.Struct("<3sBHHBBHHHHHI")
@@ -234,7 +338,10 @@ class ImageBlob(NamedTuple):
     ids: list                # T uint32 [W] views
     z: list                  # T memoryviews
     y: list
-    q: int = 0               # ladder position of the y quantiser step of every tile (0: a TMT file, else TQT)
+    q: int = 0               # ladder position of the y quantiser step of every tile (0: a TMT file, else TQT; TPT: base)
+    nlev: int = 1            # TPT: entries of the offset table (1: no map, the other magics)
+    offsets: tuple = ()      # TPT: the nlev ladder offsets of the file
+    levels: list | None = None  # TPT: T uint32 [W2] views of the tiles' level words
 
     @property
     def num_patches(self) -> int:
@@ -246,13 +353,18 @@ class ImageBlob(NamedTuple):
 
 
 def assemble_image(img_size, num_keep_patches, patch_size, lanes, z_lanes, overlap, width, height, chunk, ids_words,
-                   z_records, y_records, q=0) -> bytes:
+                   z_records, y_records, q=0, offsets=None, level_words_=None) -> bytes:
     """one TMT file from its parts; ids_words: uint32-compatible [T, W] (ops.ids_pack of the tiles), z_records /
     y_records: T byte strings each (compress_batch's records of the tiles, in tile order); q: the ladder position
-    all tiles were coded at (0: a TMT file, byte for byte; else TQT)"""
+    all tiles were coded at (0: a TMT file, byte for byte; else TQT).  offsets (2..16 ints) and level_words_
+    (uint32-compatible [T, W2], ops.qlevels_pack of the tiles): a TPT file, q its base position"""
     from .tiling import grid
 
     q = check_q(q)
+    if (offsets is None) != (level_words_ is None):
+        raise ValueError("assemble_image: offsets and level words go together")
+    if offsets is not None:
+        offsets = check_offsets(offsets, "offsets")
 
     img_size, K, patch = int(img_size), int(num_keep_patches), int(patch_size)
     overlap, width, height, chunk = int(overlap), int(width), int(height), int(chunk)
@@ -268,6 +380,12 @@ def assemble_image(img_size, num_keep_patches, patch_size, lanes, z_lanes, overl
     ids = np.ascontiguousarray(ids_words).view(np.uint32).reshape(-1, W).astype("<u4", copy=False)
     if not ids.shape[0] == len(z_records) == len(y_records) == g.T:
         raise ValueError(f"{ids.shape[0]} id rows, {len(z_records)} z and {len(y_records)} y records for {g.T} tiles")
+    lev = None
+    if offsets is not None:
+        W2 = level_words(K, len(offsets))
+        lev = np.ascontiguousarray(level_words_).view(np.uint32).reshape(-1, W2).astype("<u4", copy=False)
+        if lev.shape[0] != g.T:
+            raise ValueError(f"{lev.shape[0]} rows of level words for {g.T} tiles")
     table, body = [], []
     for t in range(g.T):
         z, y = bytes(z_records[t]), bytes(y_records[t])
@@ -275,10 +393,14 @@ def assemble_image(img_size, num_keep_patches, patch_size, lanes, z_lanes, overl
             raise ValueError(f"tile {t}: records are whole 32-bit words, at least 2 (z {len(z)} bytes, y {len(y)} "
                              f"bytes)")
         table.append(struct.pack("<II", len(z) // 4, len(y) // 4))
-        body += [ids[t].tobytes(), z, y]
+        body += [ids[t].tobytes(), z, y] if lev is None else [ids[t].tobytes(), lev[t].tobytes(), z, y]
     nib = _log2_lanes(lanes, "lanes") | _log2_lanes(z_lanes, "z_lanes") << 4
-    head = _IMAGE_HEADER.pack(IMAGE_QMAGIC if q else IMAGE_MAGIC, IMAGE_VERSION, img_size, K, patch, nib, overlap,
-                              width, height, chunk, q & 0xFF, g.T)
+    if offsets is not None:
+        head = _IMAGE_HEADER.pack(IMAGE_PMAGIC, IMAGE_VERSION, img_size, K, patch, nib, overlap, width, height, chunk,
+                                  (q & 0xFF) | len(offsets) << 8, g.T) + _offset_bytes(offsets)
+    else:
+        head = _IMAGE_HEADER.pack(IMAGE_QMAGIC if q else IMAGE_MAGIC, IMAGE_VERSION, img_size, K, patch, nib, overlap,
+                                  width, height, chunk, q & 0xFF, g.T)
     return head + b"".join(table) + b"".join(body)
 
 
@@ -304,7 +426,7 @@ def parse_image(blob) -> ImageBlob:
     if n < IMAGE_HEADER_BYTES:
         raise ValueError(f"{n} bytes: shorter than the {IMAGE_HEADER_BYTES}-byte header")
     magic, version, S, K, patch, nib, O, width, height, chunk, zero, T = _IMAGE_HEADER.unpack_from(mv, 0)
-    if magic not in (IMAGE_MAGIC, IMAGE_QMAGIC):
+    if magic not in (IMAGE_MAGIC, IMAGE_QMAGIC, IMAGE_PMAGIC):
         raise ValueError(f"not a TMT bitstream (magic {bytes(magic)!r})")
     if version != IMAGE_VERSION:
         raise ValueError(f"container version {version}, this reader knows version {IMAGE_VERSION}")
@@ -320,33 +442,43 @@ def parse_image(blob) -> ImageBlob:
         raise ValueError(f"image size {width}x{height}: width and height must be >= 1")
     if chunk == 0:
         raise ValueError("chunk 0: the encoder's tile batch must be >= 1")
-    q = _image_q(magic, zero)
+    hb, nlev, offsets = IMAGE_HEADER_BYTES, 1, ()
+    if magic == IMAGE_PMAGIC:
+        hb = IMAGE_PHEADER_BYTES
+        if n < hb:
+            raise ValueError(f"{n} bytes: shorter than the {hb}-byte TPT header")
+        q, offsets = _read_table(zero & 0xFF, zero >> 8, mv[IMAGE_HEADER_BYTES:hb], "TPT")
+        nlev = len(offsets)
+    else:
+        q = _image_q(magic, zero)
     if T > MAX_TILES:
         raise ValueError(f"{T} tiles: at most {MAX_TILES}")
     g = grid(height, width, S, O)
     if T != g.T:
         raise ValueError(f"{T} tiles, but {width}x{height} at tile size {S}, overlap {O} has {g.ny} x {g.nx} = {g.T}")
-    body0 = IMAGE_HEADER_BYTES + 8 * T
+    body0 = hb + 8 * T
     if n < body0:
         raise ValueError(f"{n} bytes: the header and the table of {T} tiles take {body0}")
-    table = np.frombuffer(mv, dtype="<u4", count=2 * T, offset=IMAGE_HEADER_BYTES).reshape(T, 2)
+    table = np.frombuffer(mv, dtype="<u4", count=2 * T, offset=hb).reshape(T, 2)
     for t in range(T):
         if table[t, 0] < 2 or table[t, 1] < 2:
             raise ValueError(f"tile {t}: z record of {table[t, 0]} and y record of {table[t, 1]} words, each holds at "
                              f"least 2")
-    W = id_words(L, K)
-    need = body0 + 4 * (T * W + int(table.sum(dtype=np.int64)))
+    W, W2 = id_words(L, K), level_words(K, nlev)
+    need = body0 + 4 * (T * (W + W2) + int(table.sum(dtype=np.int64)))
     if n != need:
         raise ValueError(f"{n} bytes: the header, the table and the {T} tiles it lists take {need}")
-    ids, zs, ys, at = [], [], [], body0
+    ids, zs, ys, lvs, at = [], [], [], [], body0
     for t in range(T):
         ids.append(np.frombuffer(mv, dtype="<u4", count=W, offset=at))
-        z0 = at + 4 * W
+        lvs.append(np.frombuffer(mv, dtype="<u4", count=W2, offset=at + 4 * W))
+        z0 = at + 4 * (W + W2)
         y0 = z0 + 4 * int(table[t, 0])
         at = y0 + 4 * int(table[t, 1])
         zs.append(mv[z0:y0])
         ys.append(mv[y0:at])
-    return ImageBlob(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids, zs, ys, q)
+    return ImageBlob(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids, zs, ys, q, nlev, offsets,
+                     lvs if nlev > 1 else None)
 
 
 class ImageIndex(NamedTuple):
@@ -367,6 +499,8 @@ class ImageIndex(NamedTuple):
     y_at: np.ndarray
     end_at: np.ndarray
     q: int = 0               # as ImageBlob.q
+    nlev: int = 1            # as ImageBlob.nlev
+    offsets: tuple = ()      # as ImageBlob.offsets; a tile's level words lie between its id words and z_at[t]
 
     @property
     def num_tiles(self) -> int:
@@ -398,8 +532,8 @@ def _source(src):
 
 def read_image_index(src) -> ImageIndex:
     """the header and the table of a TMT file without its tiles (region decode): src is a bytes-like
-    object or a seekable binary file object, of which only the 24 header bytes and the 8 * T table bytes are read
-    (the length comes from a seek to the end).  Accepts the files parse_image accepts, with its ValueErrors for
+    object or a seekable binary file object, of which only the 24 header bytes (40 of a TPT file) and the 8 * T table
+    bytes are read (the length comes from a seek to the end).  Accepts the files parse_image accepts, with its ValueErrors for
     every malformed field."""
     from .tiling import MAX_TILES, grid
 
@@ -408,7 +542,7 @@ def read_image_index(src) -> ImageIndex:
         raise ValueError(f"{n} bytes: shorter than the {IMAGE_HEADER_BYTES}-byte header")
     magic, version, S, K, patch, nib, O, width, height, chunk, zero, T = _IMAGE_HEADER.unpack(
         read(0, IMAGE_HEADER_BYTES))
-    if magic not in (IMAGE_MAGIC, IMAGE_QMAGIC):
+    if magic not in (IMAGE_MAGIC, IMAGE_QMAGIC, IMAGE_PMAGIC):
         raise ValueError(f"not a TMT bitstream (magic {bytes(magic)!r})")
     if version != IMAGE_VERSION:
         raise ValueError(f"container version {version}, this reader knows version {IMAGE_VERSION}")
@@ -424,55 +558,71 @@ def read_image_index(src) -> ImageIndex:
         raise ValueError(f"image size {width}x{height}: width and height must be >= 1")
     if chunk == 0:
         raise ValueError("chunk 0: the encoder's tile batch must be >= 1")
-    q = _image_q(magic, zero)
+    hb, nlev, offsets = IMAGE_HEADER_BYTES, 1, ()
+    if magic == IMAGE_PMAGIC:
+        hb = IMAGE_PHEADER_BYTES
+        if n < hb:
+            raise ValueError(f"{n} bytes: shorter than the {hb}-byte TPT header")
+        q, offsets = _read_table(zero & 0xFF, zero >> 8, read(IMAGE_HEADER_BYTES, hb - IMAGE_HEADER_BYTES), "TPT")
+        nlev = len(offsets)
+    else:
+        q = _image_q(magic, zero)
     if T > MAX_TILES:
         raise ValueError(f"{T} tiles: at most {MAX_TILES}")
     g = grid(height, width, S, O)
     if T != g.T:
         raise ValueError(f"{T} tiles, but {width}x{height} at tile size {S}, overlap {O} has {g.ny} x {g.nx} = {g.T}")
-    body0 = IMAGE_HEADER_BYTES + 8 * T
+    body0 = hb + 8 * T
     if n < body0:
         raise ValueError(f"{n} bytes: the header and the table of {T} tiles take {body0}")
-    table = np.frombuffer(read(IMAGE_HEADER_BYTES, 8 * T), dtype="<u4").reshape(T, 2).astype(np.int64)
+    table = np.frombuffer(read(hb, 8 * T), dtype="<u4").reshape(T, 2).astype(np.int64)
     for t in range(T):
         if table[t, 0] < 2 or table[t, 1] < 2:
             raise ValueError(f"tile {t}: z record of {table[t, 0]} and y record of {table[t, 1]} words, each holds at "
                              f"least 2")
-    W = id_words(L, K)
+    W = id_words(L, K) + level_words(K, nlev)
     end_at = body0 + 4 * np.cumsum(W + table.sum(axis=1))
     if n != end_at[-1]:
         raise ValueError(f"{n} bytes: the header, the table and the {T} tiles it lists take {end_at[-1]}")
     ids_at = np.concatenate([[body0], end_at[:-1]])
     z_at = ids_at + 4 * W
     return ImageIndex(S, K, patch, 1 << ll, 1 << zl, O, width, height, chunk, ids_at, z_at, z_at + 4 * table[:, 0],
-                      end_at, q)
+                      end_at, q, nlev, offsets)
 
 
 def read_tiles(src, index: ImageIndex, tiles):
     """(ids, z, y) of the listed tiles of the file read_image_index(src) gave the index of: per tile the uint32 [W]
-    id words and the two records, as parse_image gives them.  Reads one byte range per tile and nothing else."""
+    id words and the two records, as parse_image gives them; for a TPT file (index.nlev > 1) a fourth list follows,
+    the tiles' uint32 [W2] level words.  Reads one byte range per tile and nothing else."""
     n, read = _source(src)
     if n != index.nbytes:
         raise ValueError(f"{n} bytes, but the index is of a file of {index.nbytes}")
-    ids, zs, ys = [], [], []
+    ids, zs, ys, lvs = [], [], [], []
+    W2 = level_words(index.num_keep_patches, index.nlev)
     for t in tiles:
         t = int(t)
         if not 0 <= t < index.num_tiles:
             raise ValueError(f"tile {t} outside 0..{index.num_tiles - 1}")
         at, z0, y0, end = (int(a[t]) for a in (index.ids_at, index.z_at, index.y_at, index.end_at))
         body = memoryview(read(at, end - at))
-        ids.append(np.frombuffer(body, dtype="<u4", count=(z0 - at) // 4))
+        W = (z0 - at) // 4 - W2
+        ids.append(np.frombuffer(body, dtype="<u4", count=W))
+        lvs.append(np.frombuffer(body, dtype="<u4", count=W2, offset=4 * W))
         zs.append(body[z0 - at:y0 - at])
         ys.append(body[y0 - at:])
-    return ids, zs, ys
+    return (ids, zs, ys, lvs) if index.nlev > 1 else (ids, zs, ys)
 
 
 def tile_blob(parsed: ImageBlob, t: int) -> bytes:
-    """the version-1 TMC blob of tile t of a parsed TMT file, or the TQC blob of a tile of a TQT file (no original
-    size): what MCM.encode_bytes gives for that tile, and what parse() / MCM.decode_bytes read"""
+    """the version-1 TMC blob of tile t of a parsed TMT file, the TQC blob of a tile of a TQT file or the TPC blob of
+    a tile of a TPT file (no original size): what MCM.encode_bytes gives for that tile, and what parse() /
+    MCM.decode_bytes read"""
     p = parsed
     if not 0 <= t < p.num_tiles:
         raise ValueError(f"tile {t} outside 0..{p.num_tiles - 1}")
+    if p.nlev > 1:
+        return assemble(p.img_size, p.num_keep_patches, p.patch_size, p.lanes, p.z_lanes, None, p.ids[t], p.z[t],
+                        p.y[t], p.q, p.offsets, p.levels[t])
     return assemble(p.img_size, p.num_keep_patches, p.patch_size, p.lanes, p.z_lanes, None, p.ids[t], p.z[t], p.y[t],
                     p.q)
 
@@ -521,3 +671,90 @@ def unpack_ids_host(words, L: int, K: int):
             shuf[b] = np.concatenate([ids[b], unused])
             rest[b, shuf[b]] = np.arange(L)
     return (shuf[0], rest[0], status[0]) if one else (shuf, rest, status)
+
+
+# ------------------------------------------------------------------ per-patch quantiser steps: the kernels in numpy
+# csrc/qlevels.hip restated; integers and comparisons only, so the tests compare with equality.
+def select_levels_host(ids_shuffle, K: int, nlev: int, scores=None, level_map=None):
+    """tmae_qlevels_select in numpy: ids_shuffle int [n, L] and either scores f32 [n, L] or level_map int [n, L] ->
+    (levels int32 [n, K], status int32 [n]).  Scores: s[p] = scores[b][ids_shuffle[b][p]], rank r[p] = #{p' : s[p'] >
+    s[p] or (s[p'] == s[p] and p' < p)}, level = r nlev // K.  Map: the gathered entries; one outside 0..nlev-1 ->
+    status 1 and all-zero levels for the image"""
+    ids = np.atleast_2d(np.asarray(ids_shuffle, dtype=np.int64))
+    n, L = ids.shape
+    if not 1 <= K <= L <= MAX_L or not NLEV_MIN <= nlev <= NLEV_MAX or (scores is None) == (level_map is None):
+        raise ValueError(f"select_levels_host: need 1 <= K={K} <= L={L} <= {MAX_L}, nlev={nlev} in {NLEV_MIN}.."
+                         f"{NLEV_MAX} and exactly one of scores and level_map")
+    keep = ids[:, :K]
+    status = np.zeros(n, dtype=np.int32)
+    if level_map is not None:
+        lv = np.take_along_axis(np.asarray(level_map, dtype=np.int64).reshape(n, L), keep, axis=1)
+        bad = ((lv < 0) | (lv >= nlev)).any(axis=1)
+        status[bad] = 1
+        lv[bad] = 0
+        return lv.astype(np.int32), status
+    s = np.take_along_axis(np.asarray(scores, dtype=np.float32).reshape(n, L), keep, axis=1)
+    with np.errstate(invalid="ignore"):
+        a, b = s[:, None, :], s[:, :, None]                      # a[.., p'] against b[.., p]
+        earlier = np.arange(K)[None, None, :] < np.arange(K)[None, :, None]
+        r = ((a > b) | ((a == b) & earlier)).sum(axis=2)
+    return ((r * nlev) // K).astype(np.int32), status
+
+
+def pack_levels_host(levels, nlev: int) -> np.ndarray:
+    """levels [K] or [n, K] (each in [0, nlev)) -> uint32 words [W2] or [n, W2]: tmae_qlevels_pack in numpy"""
+    lv = np.asarray(levels, dtype=np.int64)
+    one = lv.ndim == 1
+    lv = np.atleast_2d(lv)
+    n, K = lv.shape
+    if not NLEV_MIN <= nlev <= NLEV_MAX or K < 1 or (lv < 0).any() or (lv >= nlev).any():
+        raise ValueError(f"pack_levels_host: need nlev={nlev} in {NLEV_MIN}..{NLEV_MAX} and every level in [0, nlev)")
+    bits, W = level_bits(nlev), level_words(K, nlev)
+    string = np.zeros((n, 32 * W), dtype=np.uint8)
+    string[:, :K * bits] = ((lv[:, :, None] >> np.arange(bits)) & 1).reshape(n, K * bits)
+    words = (string.reshape(n, W, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    return words[0] if one else words
+
+
+def unpack_levels_host(words, nlev, K: int):
+    """tmae_qlevels_unpack in numpy: words uint32 [n, ldw] (rows padded to a common width) and nlev int [n] (or one int
+    for all) -> (levels int32 [n, K], status int32 [n]): 0 ok, 1 a level >= nlev, 2 non-zero tail bits (the lowest that
+    applies), all-zero levels wherever it is not 0; nlev[b] == 1: no map, nothing read, all levels 0"""
+    w = np.atleast_2d(np.asarray(words)).astype(np.uint32, copy=False)
+    n, ldw = w.shape
+    nl = np.broadcast_to(np.asarray(nlev, dtype=np.int64), (n,))
+    levels = np.zeros((n, K), dtype=np.int32)
+    status = np.zeros(n, dtype=np.int32)
+    for b in range(n):
+        v = int(nl[b])
+        if v == 1:
+            continue
+        W = level_words(K, v) if 2 <= v <= NLEV_MAX else ldw + 1
+        if W > ldw:
+            status[b] = 1
+            continue
+        bits = level_bits(v)
+        string = ((w[b, :W, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(-1).astype(np.int64)
+        lv = (string[:K * bits].reshape(K, bits) << np.arange(bits)).sum(axis=1)
+        if (lv >= v).any():
+            status[b] = 1
+        elif string[K * bits:].any():
+            status[b] = 2
+        else:
+            levels[b] = lv
+    return levels, status
+
+
+def build_qmap_host(levels, q, offsets) -> np.ndarray:
+    """tmae_qmap_build in numpy: qmap[b][p] = clamp(q[b] + offsets[b][levels[b][p]], Q_MIN, Q_MAX) -> int32 [n, K];
+    levels int [n, K], q int [n] or None (all zero), offsets int [n, 16] (or one row for all images)"""
+    lv = np.atleast_2d(np.asarray(levels, dtype=np.int64))
+    n = lv.shape[0]
+    off = np.broadcast_to(np.asarray(offsets, dtype=np.int64), (n, NLEV_MAX))
+    base = np.zeros(n, dtype=np.int64) if q is None else np.broadcast_to(np.asarray(q, dtype=np.int64), (n,))
+    return np.clip(base[:, None] + np.take_along_axis(off, lv & (NLEV_MAX - 1), axis=1), Q_MIN, Q_MAX).astype(np.int32)
+
+
+def offsets_row(offsets) -> list:
+    """the 16 ints of tmae_qmap_build's table row: the offsets, then zeros (an image without a map: all zero)"""
+    return list(offsets) + [0] * (NLEV_MAX - len(offsets))

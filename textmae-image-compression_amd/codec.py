@@ -5,6 +5,7 @@
     python -m textmae_amd.codec encode --tiled [--overlap N] -c CKPT -d FOLDER -o OUT
     python -m textmae_amd.codec decode --region X,Y,W,H -c CKPT -d OUT -o PNGS
     python -m textmae_amd.codec encode [--tiled] --q N | --target-bytes N ...
+    python -m textmae_amd.codec encode [--tiled] --q-offsets A,B,C,... [--q N | --target-bytes N] ...
 
 ``encode --tiled`` codes every image at its own resolution as overlapping model-sized tiles (MCM.encode_image,
 one ``<name>.tmt`` each); ``decode`` takes ``.tmt`` files next to ``.tmc`` ones and saves them at their native size.
@@ -14,6 +15,12 @@ the window needs (MCM.decode_region); ``.tmc`` files beside them decode as befor
 ``encode --q N`` codes the y latents at the quantiser step 2^(N/8), N in -32..32: larger N, smaller
 files.  ``encode --target-bytes N`` instead picks, per file, the smallest N whose file is at most that many bytes,
 and warns about a file that does not fit even at N = 32.  The files record N; ``decode`` needs no flag.
+
+``encode --q-offsets A,B,C,...`` (2..16 integers in -64..64) codes every kept patch at its own step:
+the kept patches of an image (of a tile with ``--tiled``) are ranked by their text score, split into as many levels
+as there are offsets, the most text-like share first, and level l is coded at ladder position N + offset l (clamped
+to -32..32), N being ``--q`` (default 0) or what ``--target-bytes`` picks.  The files record the table and the
+levels; ``decode`` needs no flag.
 
 ``encode`` reads FOLDER through ``data.ImageFolderLoader`` (the test transform: bicubic resize to the model's
 size, scores from ``<FOLDER>_scores/test.pt`` or the device producer) and writes one ``<name>.tmc`` per image,
@@ -64,7 +71,7 @@ def encode_tiled(args, model):
     for p in files:
         a = np.array(Image.open(p).convert("RGB"))
         blob = model.encode_image(a, overlap=args.overlap, lanes=args.lanes, tile_batch=args.batch, q=args.q,
-                                  target_bytes=args.target_bytes)
+                                  target_bytes=args.target_bytes, qoffsets=args.q_offsets)
         _warn_target(args, p.name, blob)
         with open(os.path.join(args.output, p.stem + ".tmt"), "wb") as f:
             f.write(blob)
@@ -86,7 +93,7 @@ def encode(args):
     paths, done, nbytes = loader.imgs_path, 0, 0
     for imgs, ori_shapes, scores in loader:  # unshuffled: batch i holds paths[done : done + B]
         blobs = model.encode_bytes(imgs, scores, lanes=args.lanes, orig_sizes=ori_shapes, q=args.q,
-                                   target_bytes=args.target_bytes)
+                                   target_bytes=args.target_bytes, qoffsets=args.q_offsets)
         for p, blob in zip(paths[done:done + len(blobs)], blobs):
             _warn_target(args, p.name, blob)
             with open(os.path.join(args.output, p.stem + ".tmc"), "wb") as f:
@@ -143,6 +150,24 @@ def _region(text):
     return x0, y0, w, h
 
 
+def join_q_offsets(argv):
+    """"--q-offsets", "-8,0,4" -> "--q-offsets=-8,0,4": argparse would take a list that starts with a minus sign for
+    an option"""
+    argv, out = list(argv), []
+    while argv:
+        a = argv.pop(0)
+        out.append(a + "=" + argv.pop(0) if a == "--q-offsets" and argv else a)
+    return out
+
+
+def q_offsets(text):
+    """--q-offsets A,B,C,... -> the table of ladder offsets as a tuple (bitstream.check_offsets)"""
+    try:
+        return bitstream.check_offsets([int(v) for v in text.split(",")], "--q-offsets")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def setup_args():
     p = argparse.ArgumentParser(prog="textmae_amd.codec", description=__doc__.split("\n\n")[0])
     sub = p.add_subparsers(dest="command", required=True)
@@ -167,6 +192,9 @@ def setup_args():
                       help="quantiser step 2^(N/8) on the y latents, N in -32..32: larger N, smaller files")
     rate.add_argument("--target-bytes", type=int, default=None, metavar="N", dest="target_bytes",
                       help="per file, the smallest step whose file is at most N bytes")
+    q.add_argument("--q-offsets", type=q_offsets, default=None, metavar="A,B,C,...", dest="q_offsets",
+                   help="a quantiser step per kept patch: 2..16 ladder offsets, the first for the most text-like "
+                        "share of the kept patches (added to --q or to what --target-bytes picks)")
     sub.choices["decode"].add_argument("--original_size", action="store_true",
                                        help="save each output resized to the size its file recorded")
     sub.choices["decode"].add_argument("--region", type=_region, default=None, metavar="X,Y,W,H",
@@ -176,7 +204,7 @@ def setup_args():
 
 
 def main(argv):
-    args = setup_args().parse_args(argv)
+    args = setup_args().parse_args(join_q_offsets(argv))
     return encode(args) if args.command == "encode" else decode(args)
 
 

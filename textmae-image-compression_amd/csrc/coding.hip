@@ -99,13 +99,8 @@ extern "C" int tmae_gc_dequantize(const int* symbols, const float* mu, long long
 
 // ------------------------------------------------------------------ per-image quantiser step
 // The three kernels above with y quantised at a step delta(q[image]) of the ladder in common.h.  The per-element
-// arithmetic (gcq_quantize / gcq_recon / gcq_scale / gcq_likelihood) is in gc_q.h, shared with the forward and the
-// backward at a step.
-__device__ __forceinline__ int gcq_index(float s, const float* __restrict__ scale_table, int nscale) {
-  int id = nscale - 1;
-  for (int t = 0; t < nscale - 1; ++t) id -= (s <= scale_table[t]) ? 1 : 0;
-  return id;
-}
+// arithmetic (gcq_quantize / gcq_recon / gcq_scale / gcq_likelihood / gcq_index) is in gc_q.h, shared with the forward
+// and the backward at a step and with the kernels at a step per patch (coding_qmap.hip, §3.19).
 
 // one element per thread (maps past the LDS tile): gc_slices_kernel<YT, true>'s indexing
 template <typename YT>

@@ -26,6 +26,13 @@ __device__ __forceinline__ GcqElem gcq_quantize(float yv, float mv, float sv, fl
   return GcqElem{qi, gcq_recon(qi, mv, delta), gcq_scale(sv, delta, bound)};
 }
 
+// build_indexes on the scale at a step (shared by coding.hip and coding_qmap.hip)
+__device__ __forceinline__ int gcq_index(float s, const float* __restrict__ scale_table, int nscale) {
+  int id = nscale - 1;
+  for (int t = 0; t < nscale - 1; ++t) id -= (s <= scale_table[t]) ? 1 : 0;
+  return id;
+}
+
 // the symbol's probability mass under N(0, s): the table entry the coder approximates
 __device__ __forceinline__ float gcq_likelihood(float qi, float s) {
   const float val = fabsf(qi);

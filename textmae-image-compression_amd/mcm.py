@@ -194,7 +194,7 @@ class MCM(CompressionModel):
         ex.refresh_weights()
         return ex
 
-    def forward(self, imgs, total_scores, noise=None, q=None):
+    def forward(self, imgs, total_scores, noise=None, q=None, qoffsets=None, qlevels=None):
         """MCM.forward (MCM.py:714-803).  `noise=(z_noise, y_noise)` (NCHW, U(-1/2, 1/2)) replaces the
         training-mode quantisation noise — used by parity tests; otherwise drawn on the device.
 
@@ -203,15 +203,25 @@ class MCM(CompressionModel):
         2^(q/8) with the coder's arithmetic: in eval x_hat is bitwise decompress_batch(compress_batch(q=), q=)'s and
         the y likelihoods are the coded symbols' masses; under autograd the backward is that forward's.  None, or host
         values that are all zero, is the path without q with its kernels and bits.  A device tensor is taken as given
-        (not read back, so the call can be captured into a graph) and always runs the kernels with a step."""
+        (not read back, so the call can be captured into a graph) and always runs the kernels with a step.
+
+        qoffsets / qlevels (eval only): compress_batch's table of ladder offsets and source of the
+        per-patch levels; y is then quantised at a step per kept patch, q being the base position.  x_hat and the y
+        likelihoods are bit for bit what the coder reconstructs and codes with the same arguments.  The slice loop
+        runs unchained.  Under autograd or in training mode ValueError: training with a map is not implemented."""
         q = self._forward_q(q, imgs.shape[0])
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        qm = self._check_qoffsets(qoffsets, qlevels, imgs.shape[0], self._geometry()[3], "forward")
+        if qm is not None and (train or self.training):
+            raise ValueError("forward: qoffsets is for evaluation (model.eval() under torch.no_grad()); training with "
+                             "a map of quantiser steps is not implemented")
         if not imgs.is_cuda:
             raise ValueError("MCM.forward runs on the MI355X kernels: move the model and inputs to the GPU")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if train:
             return self._forward_train(imgs, total_scores, noise, q)
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            out = ex.run(imgs, total_scores, self.training, noise, q=q)
+            out = ex.run(imgs, total_scores, self.training, noise, q=q, qm=qm)
             x_hat = out["x_hat"]
             loss = self.forward_loss(imgs, x_hat) if self.distortion != "none" else (ex.zero_loss,) * 3
         return {"loss": loss, "likelihoods": {"y": out["y"], "z": out["z"]}, "x_hat": x_hat}
@@ -389,7 +399,40 @@ class MCM(CompressionModel):
             qs = [check_q(v, f"{who}: q[{b}]") for b, v in enumerate(qs)]
         return qs if any(qs) else None
 
-    def compress_batch(self, imgs, total_scores, lanes=1, z_lanes=None, q=None):
+    @staticmethod
+    def _check_qoffsets(qoffsets, qlevels, B, L, who, K=None):
+        """qoffsets= / qlevels= of the batch methods -> None (no map) or (the offsets as a tuple, the source of the
+        levels): "scores", an int32 numpy array checked here, or the caller's device tensor (checked on the device).
+        The array is [B, L] in image patch order; with K (decompress_batch) also [B, K] in kept order.  ValueError
+        before anything is launched"""
+        from .bitstream import check_offsets
+
+        if qoffsets is None:
+            if qlevels is not None:
+                raise ValueError(f"{who}: qlevels without qoffsets (the table the levels index)")
+            return None
+        offs = check_offsets(qoffsets, f"{who}: qoffsets")
+        if isinstance(qlevels, str) or qlevels is None:
+            if qlevels not in (None, "scores") or K is not None:
+                raise ValueError(f"{who}: qlevels = {qlevels!r}: " + ("the levels compress_batch returned, or an int "
+                                 f"map [{B}, {L}]" if K is not None else f"'scores' or an int map [{B}, {L}]"))
+            return offs, "scores"
+        shapes = [(B, L)] + ([(B, K)] if K is not None else [])
+        if torch.is_tensor(qlevels) and qlevels.is_cuda:
+            if qlevels.dtype != torch.int32 or tuple(qlevels.shape) not in shapes or not qlevels.is_contiguous():
+                raise ValueError(f"{who}: a device qlevels must be a contiguous int32 {list(shapes[0])} tensor, got "
+                                 f"{qlevels.dtype} {tuple(qlevels.shape)}")
+            return offs, qlevels
+        a = np.asarray(qlevels.numpy() if torch.is_tensor(qlevels) else qlevels)
+        if a.shape not in shapes or a.dtype.kind not in "iu":
+            raise ValueError(f"{who}: qlevels must be 'scores' or an integer map {list(shapes[0])} in image patch "
+                             f"order, got {a.dtype} {a.shape}")
+        bad = np.flatnonzero(((a < 0) | (a >= len(offs))).any(axis=1))
+        if bad.size:
+            raise ValueError(f"{who}: qlevels of image {int(bad[0])}: a level outside 0..{len(offs) - 1}")
+        return offs, np.ascontiguousarray(a, dtype=np.int32)
+
+    def compress_batch(self, imgs, total_scores, lanes=1, z_lanes=None, q=None, qoffsets=None, qlevels=None):
         """compress with one independent record per image, coded on the device (csrc/rans_device.hip) ->
         {"string": [y_strings, z_strings], "shape", "ids_restore"}, len(y_strings) == len(z_strings) == B.
         Image b's (y_strings[b], z_strings[b]) are the strings MCM.compress (MCM.py:805-894) returns for that image
@@ -403,25 +446,37 @@ class MCM(CompressionModel):
         q: ladder positions of the y quantiser step, an int or a sequence of B ints in -32..32
         (bitstream.qstep: step 2^(q/8), 1/16 .. 16); image b's y symbols are round((y - mu) / step_b) and its record
         grows as q falls.  None, or all zero, is the path above with its kernels and bytes; decompress_batch needs
-        the same q.  z is not scaled."""
+        the same q.  z is not scaled.
+
+        qoffsets: a table of 2..16 ladder offsets, integers in -64..64; every kept patch p then
+        has a level l[p] into it and its y elements are coded at ladder position clamp(q + qoffsets[l[p]], -32, 32),
+        q being the base (None: 0).  qlevels: "scores" (the default: the kept patches ranked by their score, level 0
+        the most text-like share) or an integer map [B, L] in image patch order (the layout of total_scores), a numpy
+        array or an int32 device tensor; an entry outside the table raises ValueError naming the image.  The result
+        then carries "qoffsets" and "qlevels" (int32 [B, K] on the device, kept order), which decompress_batch needs
+        together with q."""
         from .coder import check_lanes
 
         lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
         q = self._check_q(q, imgs.shape[0], "compress_batch")
+        qm = self._check_qoffsets(qoffsets, qlevels, imgs.shape[0], self._geometry()[3], "compress_batch")
         if not imgs.is_cuda:
             raise ValueError("MCM.compress_batch runs on the MI355X kernels: move the model and inputs to the GPU")
         self.entropy_bottleneck._check_cdf()
         self.gaussian_conditional._check_cdf()
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            return ex.compress_batch(imgs, total_scores, lanes, z_lanes, q)
+            return ex.compress_batch(imgs, total_scores, lanes, z_lanes, q, qm=qm)
 
-    def decompress_batch(self, strings, shape, ids_restore=None, lanes=1, z_lanes=None, q=None):
+    def decompress_batch(self, strings, shape, ids_restore=None, lanes=1, z_lanes=None, q=None, qoffsets=None,
+                         qlevels=None):
         """inverse of compress_batch -> {"x_hat"}: strings = [y_strings, z_strings], one of each per image.  The
         streams are decoded on the device inside the slice loop; a corrupt stream raises ValueError naming its image
         after the whole batch has been enqueued.  lanes / z_lanes are compress_batch's; a record whose header does
         not fit them raises ValueError naming its image before anything is launched.  q: compress_batch's (an int or
-        one per image), checked before anything is launched as well."""
+        one per image), checked before anything is launched as well.  qoffsets / qlevels: compress_batch's table and
+        the "qlevels" it returned (int [B, K], kept order), or an integer map [B, L] in image patch order (at K = L an
+        array is taken to be in kept order)."""
         from .coder import check_lanes
 
         lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
@@ -431,6 +486,8 @@ class MCM(CompressionModel):
         if len(strings[0]) != len(strings[1]):
             raise ValueError(f"{len(strings[0])} y strings but {len(strings[1])} z strings: one of each per image")
         q = self._check_q(q, len(strings[1]), "decompress_batch")
+        _, _, K, L = self._geometry()
+        qm = self._check_qoffsets(qoffsets, qlevels, len(strings[1]), L, "decompress_batch", K=K)
         self.entropy_bottleneck._check_cdf()
         self.gaussian_conditional._check_cdf()
         dev = next(self.parameters()).device
@@ -438,14 +495,17 @@ class MCM(CompressionModel):
             raise ValueError("MCM.decompress_batch runs on the MI355X kernels: move the model to the GPU")
         with torch.no_grad():
             ex = self._executor(len(strings[1]), dev)
-            return {"x_hat": ex.decompress_batch(strings, shape, ids_restore, lanes, z_lanes, q=q)}
+            if qm is not None:
+                qm = ex.decode_map(qm, ids_restore)
+            return {"x_hat": ex.decompress_batch(strings, shape, ids_restore, lanes, z_lanes, q=q, qm=qm)}
 
     def _geometry(self):
         """(img_size, patch_size, num_keep_patches, L) as the container header states them"""
         pe = self.encoder_embed
         return int(pe.img_size[0]), int(pe.patch_size[0]), int(self.num_keep_patches), int(pe.num_patches)
 
-    def encode_bytes(self, imgs, total_scores, lanes=1, z_lanes=None, orig_sizes=None, q=None, target_bytes=None):
+    def encode_bytes(self, imgs, total_scores, lanes=1, z_lanes=None, orig_sizes=None, q=None, target_bytes=None,
+                     qoffsets=None, qlevels=None):
         """compress_batch into self-contained bitstreams -> list of B bytes objects (bitstream.py, container version
         1): header (geometry, lanes, original size), the kept patch ids packed on the device (ops.ids_pack, at
         ceil(log2 L) bits each), then compress_batch's z and y records of the image as they are.  decode_bytes needs
@@ -457,7 +517,12 @@ class MCM(CompressionModel):
         -32..32 for all images at once, at most 7 probes, each of which repeats only the slice loop and the y coder
         (the analysis up to h_s runs once).  The blob kept is the one of the image's smallest successful probe.  The
         size is taken to be non-increasing in q; an image that does not fit at q = 32 gets its q = 32 blob, longer
-        than the target.  q together with target_bytes raises ValueError."""
+        than the target.  q together with target_bytes raises ValueError.
+
+        qoffsets / qlevels: compress_batch's; every image then becomes a TPC blob that records its
+        base q (0 included), the table and the levels of its kept patches, packed on the device (ops.qlevels_pack).
+        With target_bytes the bisection runs over the base q as above, the map being rebuilt per probe, and the size
+        counts the TPC header and the level words."""
         from . import bitstream
 
         B = imgs.shape[0]
@@ -466,16 +531,21 @@ class MCM(CompressionModel):
         if q is not None and target_bytes is not None:
             raise ValueError("encode_bytes: give q or target_bytes, not both")
         img, patch, K, L = self._geometry()
+        qm = self._check_qoffsets(qoffsets, qlevels, B, L, "encode_bytes")
         if target_bytes is not None:
             fixed = 4 * bitstream.id_words(L, K)
-            lanes, z_lanes, ids, z, y, qs = self._encode_sections_target(
-                imgs, total_scores, lanes, z_lanes, self._check_targets(target_bytes, B, "encode_bytes"),
-                lambda v: (bitstream.QHEADER_BYTES if v else bitstream.HEADER_BYTES) + fixed)
+            if qm is None:
+                size = lambda v: (bitstream.QHEADER_BYTES if v else bitstream.HEADER_BYTES) + fixed  # noqa: E731
+            else:
+                size = lambda v: bitstream.PHEADER_BYTES + fixed + 4 * bitstream.level_words(K, len(qm[0]))  # noqa: E731
+            lanes, z_lanes, ids, z, y, qs, lev = self._encode_sections_target(
+                imgs, total_scores, lanes, z_lanes, self._check_targets(target_bytes, B, "encode_bytes"), size, qm)
         else:
             qs = self._check_q(q, B, "encode_bytes") or [0] * B
-            lanes, z_lanes, ids, z, y = self._encode_sections(imgs, total_scores, lanes, z_lanes, qs)
+            lanes, z_lanes, ids, z, y, lev = self._encode_sections(imgs, total_scores, lanes, z_lanes, qs, qm)
         return [bitstream.assemble(img, K, patch, lanes, z_lanes, None if orig_sizes is None else orig_sizes[b],
-                                   ids[b], z[b], y[b], qs[b]) for b in range(B)]
+                                   ids[b], z[b], y[b], qs[b], *(() if qm is None else (qm[0], lev[b])))
+                for b in range(B)]
 
     @staticmethod
     def _check_targets(target_bytes, B, who):
@@ -486,18 +556,30 @@ class MCM(CompressionModel):
             raise ValueError(f"{who}: {len(t)} entries of target_bytes for {B} images: one per image, or one int")
         return t
 
-    def _encode_sections(self, imgs, total_scores, lanes, z_lanes, q=None):
-        """the sections of encode_bytes' blobs (and of encode_image's tiles) -> (lanes, z_lanes, id words uint32-
-        compatible numpy [B, W], z records, y records): compress_batch, then the kept ids packed on the device"""
-        out = self.compress_batch(imgs, total_scores, lanes, z_lanes, q)
-        lanes, z_lanes = out.get("lanes", (1, 1))
-        ids = ops.ids_pack(self._exec.last_ids_shuffle, self._geometry()[2]).cpu().numpy()  # the one extra copy
-        y, z = out["string"]
-        return lanes, z_lanes, ids, z, y
+    def _side_words(self, qm):
+        """the id words and, with a map, the level words of the batch just coded, packed on the device -> (uint32-
+        compatible numpy [B, W], [B, W2] or None): one copy for both"""
+        K = self._geometry()[2]
+        ids = ops.ids_pack(self._exec.last_ids_shuffle, K)
+        if qm is None:
+            return ids.cpu().numpy(), None  # the one extra copy
+        W = ids.shape[1]
+        both = torch.cat([ids, ops.qlevels_pack(self._exec.last_levels, len(qm[0]))], dim=1).cpu().numpy()
+        return both[:, :W], both[:, W:]
 
-    def _encode_sections_target(self, imgs, total_scores, lanes, z_lanes, targets, fixed_bytes):
-        """_encode_sections with per image the smallest q whose blob fits targets[b] -> (..., y records, q per image);
-        fixed_bytes(q): the bytes of a blob at q besides its z and y records"""
+    def _encode_sections(self, imgs, total_scores, lanes, z_lanes, q=None, qm=None):
+        """the sections of encode_bytes' blobs (and of encode_image's tiles) -> (lanes, z_lanes, id words uint32-
+        compatible numpy [B, W], z records, y records, level words [B, W2] or None): compress_batch, then the kept ids
+        (and with a map qm = _check_qoffsets' pair the levels) packed on the device"""
+        out = self.compress_batch(imgs, total_scores, lanes, z_lanes, q, *((None, None) if qm is None else qm))
+        lanes, z_lanes = out.get("lanes", (1, 1))
+        ids, lev = self._side_words(qm)
+        y, z = out["string"]
+        return lanes, z_lanes, ids, z, y, lev
+
+    def _encode_sections_target(self, imgs, total_scores, lanes, z_lanes, targets, fixed_bytes, qm=None):
+        """_encode_sections with per image the smallest q whose blob fits targets[b] -> (..., y records, q per image,
+        level words); fixed_bytes(q): the bytes of a blob at q besides its z and y records"""
         from .coder import check_lanes
 
         lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
@@ -507,17 +589,29 @@ class MCM(CompressionModel):
         self.gaussian_conditional._check_cdf()
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            z, y, qs = ex.compress_batch_target(imgs, total_scores, lanes, z_lanes, targets, fixed_bytes)
-        ids = ops.ids_pack(self._exec.last_ids_shuffle, self._geometry()[2]).cpu().numpy()
-        return lanes, z_lanes, ids, z, y, qs
+            z, y, qs = ex.compress_batch_target(imgs, total_scores, lanes, z_lanes, targets, fixed_bytes, qm=qm)
+        ids, lev = self._side_words(qm)
+        return lanes, z_lanes, ids, z, y, qs, lev
 
-    def _decode_sections(self, ids, z, y, lanes, z_lanes, who, q=None):
+    def _decode_sections(self, ids, z, y, lanes, z_lanes, who, q=None, maps=None):
         """inverse of _encode_sections -> x_hat [B, 3, S, S]: the id words (B uint32 [W] rows) go up, ops.ids_unpack
         validates and completes them on the device, the records take the decompress_batch path and the ids status
         words are read with the coder's.  who: the calling method's name for the error message; q: the images' ladder
-        positions as their containers state them (None: all zero)"""
+        positions as their containers state them (None: all zero); maps: per image (nlev, offsets, level words) as
+        its container states them (nlev = 1: no map), or None when no image has one.  With a map the level words go
+        up with their per-image table sizes, ops.qlevels_unpack validates them and an image without a map gets a
+        constant one"""
+        from . import bitstream
+
         _, _, K, L = self._geometry()
-        q = self._check_q(q, len(ids), who)
+        B = len(ids)
+        if maps is not None and all(m[0] == 1 for m in maps):
+            maps = None
+        if maps is None:
+            q = self._check_q(q, B, who)
+        else:
+            q = [0] * B if q is None else ([bitstream.check_q(q)] * B if np.ndim(q) == 0 else
+                                           [bitstream.check_q(v) for v in q])
         self.entropy_bottleneck._check_cdf()
         self.gaussian_conditional._check_cdf()
         dev = next(self.parameters()).device
@@ -525,11 +619,23 @@ class MCM(CompressionModel):
             raise ValueError(f"MCM.{who} runs on the MI355X kernels: move the model to the GPU")
         strings = [[bytes(s) for s in y], [bytes(s) for s in z]]
         words = torch.from_numpy(np.stack(ids).view(np.int32)).to(dev)
+        qm = None
+        if maps is not None:
+            ldw = max(bitstream.level_words(K, m[0]) for m in maps)
+            lw = np.zeros((B, ldw), dtype=np.uint32)
+            for b, m in enumerate(maps):
+                if m[0] > 1:
+                    lw[b, :bitstream.level_words(K, m[0])] = m[2]
+            table = np.array([[m[0]] + bitstream.offsets_row(m[1]) for m in maps], dtype=np.int32)
+            lw, table = torch.from_numpy(lw.view(np.int32)).to(dev), torch.from_numpy(table).to(dev)
         with torch.no_grad():
             ex = self._executor(len(ids), dev)
             _, rest, status = ops.ids_unpack(words, L, K)
+            if maps is not None:
+                levels, lstatus = ops.qlevels_unpack(lw, table[:, 0].contiguous(), K)
+                qm = dict(levels=levels, status=lstatus, offsets=table[:, 1:].contiguous())
             return ex.decompress_batch(strings, torch.Size([ex.hz, ex.hz]), rest, lanes, z_lanes, ids_status=status,
-                                       q=q)
+                                       q=q, qm=qm)
 
     def decode_bytes(self, blobs):
         """inverse of encode_bytes -> {"x_hat": [B, 3, S, S], "orig_sizes": [(width, height) or None per image]}.
@@ -539,8 +645,10 @@ class MCM(CompressionModel):
         completes them into ids_restore on the device, and the records take the decompress_batch path; the ids
         status words are read with the coder's after everything is enqueued, and an image whose side information is
         corrupt (decoded harmlessly with the identity permutation) raises ValueError("side information of image b").
-        Each blob states the quantiser step it was coded at (TMC: 1, TQC: its q); blobs of different
-        steps, plain ones among them, decode together in one call."""
+        Each blob states the quantiser step it was coded at (TMC: 1, TQC: its q; TPC: its base q,
+        table and per-patch levels, §3.19); blobs of different steps and kinds decode together in one call, an image
+        without a map taking a constant one.  A corrupt level section (decoded harmlessly with all levels zero) raises
+        ValueError("side information of image b") like corrupt ids."""
         from . import bitstream
 
         blobs = list(blobs)
@@ -561,10 +669,12 @@ class MCM(CompressionModel):
                                  f"({parsed[0].lanes}, {parsed[0].z_lanes}): decode them in separate calls")
             parsed.append(p)
         x_hat = self._decode_sections([p.ids for p in parsed], [p.z for p in parsed], [p.y for p in parsed],
-                                      parsed[0].lanes, parsed[0].z_lanes, "decode_bytes", [p.q for p in parsed])
+                                      parsed[0].lanes, parsed[0].z_lanes, "decode_bytes", [p.q for p in parsed],
+                                      [(p.nlev, p.offsets, p.levels) for p in parsed])
         return {"x_hat": x_hat, "orig_sizes": [p.orig_size for p in parsed]}
 
-    def encode_image(self, rgb_u8, overlap=32, lanes=1, z_lanes=None, tile_batch=16, q=None, target_bytes=None):
+    def encode_image(self, rgb_u8, overlap=32, lanes=1, z_lanes=None, tile_batch=16, q=None, target_bytes=None,
+                     qoffsets=None):
         """an image at its own resolution -> one TMT file (bitstream.assemble_image).  rgb_u8: uint8
         [H, W, 3], numpy or tensor (a host image is uploaded once).  The image is cut into overlapping model-sized
         tiles (tiling.py; overlap 0..img_size // 2) and every chunk of tile_batch tiles (the last may be smaller)
@@ -576,7 +686,11 @@ class MCM(CompressionModel):
         that records it, q = 0 or None the TMT file as before.  target_bytes instead picks the smallest q whose
         whole file is at most that many bytes, by the lower-bound bisection of encode_bytes on the file size (at
         most 7 probes); here every probe codes the image anew, analysis included, and an image that
-        does not fit at q = 32 gets its q = 32 file.  q together with target_bytes raises ValueError."""
+        does not fit at q = 32 gets its q = 32 file.  q together with target_bytes raises ValueError.
+
+        qoffsets: compress_batch's table of ladder offsets; every tile's kept patches get their
+        levels from the tile's own scores and the file becomes a TPT file with that one table, q (or the q that
+        target_bytes picks) its base position."""
         from . import bitstream, tiling
         from .coder import check_lanes
         from .scores import image_scores
@@ -597,21 +711,23 @@ class MCM(CompressionModel):
         if q is not None and target_bytes is not None:
             raise ValueError("encode_image: give q or target_bytes, not both")
         q = 0 if q is None else bitstream.check_q(q, "encode_image: q")
+        qm = self._check_qoffsets(qoffsets, None, 1, 1, "encode_image")
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise ValueError("MCM.encode_image runs on the MI355X kernels: move the model to the GPU")
         x = x.to(dev).contiguous()
 
         def code(qv):
-            ids, zs, ys = [], [], []
+            ids, zs, ys, lvs = [], [], [], []
             for t0 in range(0, g.T, tile_batch):
                 tiles, gray = ops.tile_cut_u8(x, img, g.O, t0, min(tile_batch, g.T - t0))
-                _, _, i, z, y = self._encode_sections(tiles, image_scores(gray, img, patch), lanes, z_lanes, qv)
+                _, _, i, z, y, lv = self._encode_sections(tiles, image_scores(gray, img, patch), lanes, z_lanes, qv, qm)
                 ids.append(i)
+                lvs.append(lv)
                 zs += list(z)
                 ys += list(y)
             return bitstream.assemble_image(img, K, patch, lanes, z_lanes, g.O, W, H, tile_batch, np.concatenate(ids),
-                                            zs, ys, qv)
+                                            zs, ys, qv, *(() if qm is None else (qm[0], np.concatenate(lvs))))
 
         if target_bytes is None:
             return code(q)
@@ -651,7 +767,9 @@ class MCM(CompressionModel):
             t1 = min(t0 + n, T)
             try:
                 x_hat = self._decode_sections(p.ids[t0:t1], p.z[t0:t1], p.y[t0:t1], p.lanes, p.z_lanes,
-                                              "decode_image", p.q)
+                                              "decode_image", p.q,
+                                              None if p.nlev == 1 else [(p.nlev, p.offsets, lv)
+                                                                        for lv in p.levels[t0:t1]])
             except ValueError as e:  # the batch path names the image of its call: that is tile t0 + b of the file
                 raise ValueError(re.sub(r"\bimage (\d+)", lambda m: f"tile {t0 + int(m.group(1))}", str(e), count=1)
                                  ) from None
@@ -676,7 +794,8 @@ class MCM(CompressionModel):
         [R, 3, h, w] or uint8 [R, h, w, 3], each window decode_region's.  srcs may hold the same object several
         times: per distinct source the union of the tiles its windows need is read and decoded once.  The tiles of
         all sources are batched together in chunks of tile_batch (sources coded with other lanes in batches of
-        their own, files of different quantiser steps in one batch) and one ops.tile_blend_crops produces all
+        their own, files of different quantiser steps, with a per-patch table or without, in one batch) and one
+        ops.tile_blend_crops produces all
         windows.  ValueErrors as decode_region, naming the source by its first position in srcs; the sources of one
         call must agree in their overlap."""
         srcs, origins = list(srcs), list(origins)
@@ -732,8 +851,9 @@ class MCM(CompressionModel):
         sections = {}
         for k, p in enumerate(index):
             tiles_k = sorted(need[k])
-            for t, i, z, y in zip(tiles_k, *bitstream.read_tiles(srcs[where[k]], p, tiles_k)):
-                sections[k, t] = (i, z, y)
+            got = bitstream.read_tiles(srcs[where[k]], p, tiles_k)
+            for j, t in enumerate(tiles_k):  # a file with a map has a fourth list, the level words
+                sections[k, t] = (got[0][j], got[1][j], got[2][j], got[3][j] if p.nlev > 1 else None)
         n = index[0].chunk if n is None else n
         job_lanes = [(index[k].lanes, index[k].z_lanes) for k, _ in jobs]
         tiles, s0 = None, 0
@@ -745,7 +865,9 @@ class MCM(CompressionModel):
             part = [sections[j] for j in jobs[s0:s1]]
             try:
                 x_hat = self._decode_sections([a[0] for a in part], [a[1] for a in part], [a[2] for a in part],
-                                              lanes[0], lanes[1], who, [index[k].q for k, _ in jobs[s0:s1]])
+                                              lanes[0], lanes[1], who, [index[k].q for k, _ in jobs[s0:s1]],
+                                              [(index[k].nlev, index[k].offsets, a[3])
+                                               for (k, _), a in zip(jobs[s0:s1], part)])
             except ValueError as e:  # the batch path names the image of its call: that is job s0 + b
 
                 def name(m, s0=s0):
@@ -1016,10 +1138,13 @@ class _Executor:
             raise ValueError(f"Input image size {tuple(imgs.shape[2:])} doesn't match model ({self.img})")
         return imgs
 
-    def run(self, imgs, scores, training, noise, q=None):
-        """q: None, B ladder positions (uploaded once, before the first launch) or an int32 [B] device tensor"""
+    def run(self, imgs, scores, training, noise, q=None, qm=None):
+        """q: None, B ladder positions (uploaded once, before the first launch) or an int32 [B] device tensor; qm:
+        MCM._check_qoffsets' pair (eval only): the slice loop then runs unchained at a step per kept patch"""
         m, B = self.m, self.batch
         qd = self._q_dev(q)
+        if qm is not None:
+            qm = self._map_upload(qm)
         M, N, g, hz = m.latent_depth, m.hyperprior_depth, self.g, self.hz
         imgs = self._check_imgs(imgs)
         if training:
@@ -1044,9 +1169,15 @@ class _Executor:
         self._h_s()
 
         # ---- slice loop (MCM.py:751-787)
-        self._slices(self._gc_forward(y_noise, qd), chain_ok=True, cq=qd)
+        if qm is None:
+            self._slices(self._gc_forward(y_noise, qd), chain_ok=True, cq=qd)
+        else:
+            qmap, lstatus = self._encode_map(qm, scores, shuf, qd)
+            self._slices(self._gc_forward(y_noise, None, qmap))
 
         x_hat = self._back(shuf, imgs.shape[1])
+        if qm is not None and lstatus is not None:
+            self._raise_levels(lstatus.cpu().numpy(), "forward")
         return {"x_hat": x_hat, "y": self.YLIK, "z": self.ZLIK, "ids_restore": rest,
                 "ids_shuffle": shuf}
 
@@ -1093,11 +1224,62 @@ class _Executor:
             return q
         return torch.tensor(q, dtype=torch.int32).to(self.device)
 
-    def _analysis(self, imgs, scores, qd=None):
+    # ------------------------------------------------------------------ per-patch quantiser steps
+    def _map_upload(self, qm):
+        """MCM._check_qoffsets' pair with everything of it that lives on the host uploaded (before the first launch)
+        -> (offsets tuple, "scores" | int32 device tensor, device offsets [B, 16], whether the device checks the map)"""
+        from .bitstream import offsets_row
+
+        offs, src = qm
+        rows = torch.tensor([offsets_row(offs)] * self.batch, dtype=torch.int32).to(self.device)
+        on_device = torch.is_tensor(src)
+        if isinstance(src, np.ndarray):
+            src = torch.from_numpy(src).to(self.device)
+        return offs, src, rows, on_device
+
+    def _select_levels(self, qm, scores, shuf):
+        """the levels of the kept patches -> (levels int32 [B, K], status int32 [B] or None when nothing can be wrong)"""
+        offs, src, _, on_device = qm
+        K = self.m.num_keep_patches
+        if isinstance(src, str):
+            levels, _ = ops.qlevels_select(shuf, K, len(offs), scores=scores.float().contiguous())
+            return levels, None
+        levels, status = ops.qlevels_select(shuf, K, len(offs), level_map=src)
+        return levels, status if on_device else None
+
+    def _encode_map(self, qm, scores, shuf, qd):
+        """levels from the scores or the caller's map, then the map of clamped ladder positions at the base qd ->
+        (qmap int32 [B, K], status or None); the levels stay in self.last_levels for the side information"""
+        self.last_levels, status = self._select_levels(qm, scores, shuf)
+        return ops.qmap_build(self.last_levels, qd, qm[2]), status
+
+    @staticmethod
+    def _raise_levels(status, who):
+        for b in np.flatnonzero(status):
+            raise ValueError(f"{who}: qlevels of image {int(b)}: a level outside its table of offsets")
+
+    def decode_map(self, qm, ids_restore):
+        """decompress_batch's qoffsets / qlevels -> the dict its executor method takes: levels in kept order as they
+        are, a map in image patch order gathered by ids_shuffle"""
+        offs, src, rows, on_device = self._map_upload(qm)
+        K = self.m.num_keep_patches
+        status = None
+        if src.shape[1] == K:
+            levels = src
+        else:
+            shuf = ops.invert_permutation(ids_restore.to(self.device))
+            levels, status = ops.qlevels_select(shuf, K, len(offs), level_map=src)
+        return dict(levels=levels, status=status if on_device else None, offsets=rows, who="qlevels")
+
+    def _analysis(self, imgs, scores, qd=None, qm=None):
         """the eval forward's analysis path with symbol / index outputs -> (zsym [B][N][hz*hz], y sym and idx
-        [slice][image][channel][pixel], ids_restore), all on the device; qd: _q_dev's positions"""
+        [slice][image][channel][pixel], ids_restore), all on the device; qd: _q_dev's positions; qm: _map_upload's
+        tuple, the levels' status then in self.last_levels_status"""
         zsym, rest = self._analysis_head(imgs, scores)
-        sym, idx = self._analysis_slices(qd)
+        qmap = None
+        if qm is not None:
+            qmap, self.last_levels_status = self._encode_map(qm, scores, self.last_ids_shuffle, qd)
+        sym, idx = self._analysis_slices(qd, qmap)
         return zsym, sym, idx, rest
 
     def _analysis_head(self, imgs, scores):
@@ -1114,14 +1296,14 @@ class _Executor:
         self._h_s()
         return zsym, rest
 
-    def _analysis_slices(self, qd=None):
+    def _analysis_slices(self, qd=None, qmap=None):
         """the slice loop of _analysis on what _analysis_head left (Y32, the h_s outputs) -> (sym, idx); it may be
-        run again at another qd: nothing it reads is written by it"""
+        run again at another qd or qmap (int32 [B, K], which takes precedence): nothing it reads is written by it"""
         m, B = self.m, self.batch
         S, sw, HW = m.num_slices, self.sw, self.g * self.g
         sym = torch.empty(S * B * sw * HW, dtype=torch.int32, device=self.device)
         idx = torch.empty_like(sym)
-        self._slices(self._gc_compress(sym, idx, qd))
+        self._slices(self._gc_compress(sym, idx, qd, qmap))
         return sym, idx
 
     def _code_z(self, zsym, z_lanes):
@@ -1143,38 +1325,52 @@ class _Executor:
             enc = self._dev_encoder = DeviceRansEncoder()
         return enc
 
-    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1, q=None):
+    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1, q=None, qm=None):
         """compress with the device coder: the same symbol / index buffers, coded as one y and one z record per
         image (image b's y stream = its [slice][channel][pixel] symbols) of lanes / z_lanes lanes
         (coder.encode_record); one lane is the plain stream, the reference's batch-1 format B times.  q: None or B
-        ladder positions, uploaded once before the first launch"""
+        ladder positions, uploaded once before the first launch; qm: MCM._check_qoffsets' pair
+        (§3.19)"""
         hz = self.hz
-        zsym, sym, idx, rest = self._analysis(imgs, scores, self._q_dev(q))
+        qd = self._q_dev(q)
+        if qm is not None:
+            qm = self._map_upload(qm)
+        zsym, sym, idx, rest = self._analysis(imgs, scores, qd, qm)
         z_strings = self._code_z(zsym, z_lanes)
         y_strings = self._code_y(sym, idx, lanes)
         self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # rate diagnostics
         out = {"string": [y_strings, z_strings], "shape": torch.Size([hz, hz]), "ids_restore": rest}
+        if qm is not None:
+            if self.last_levels_status is not None:
+                self._raise_levels(self.last_levels_status.cpu().numpy(), "compress_batch")
+            out["qoffsets"], out["qlevels"] = qm[0], self.last_levels
         if lanes > 1 or z_lanes > 1:
             out["lanes"] = (lanes, z_lanes)
         return out
 
-    def compress_batch_target(self, imgs, scores, lanes, z_lanes, targets, fixed_bytes):
+    def compress_batch_target(self, imgs, scores, lanes, z_lanes, targets, fixed_bytes, qm=None):
         """compress_batch with per image the smallest q of the ladder at which fixed_bytes(q) + its z record + its y
         record is at most targets[b] -> (z records, y records, q per image).  Lower-bound bisection over Q_MIN..Q_MAX
         for all images at once (hi = Q_MAX + 1 stands for "no q fits" and is never probed): at most 7 probes, each the
         slice loop and the y coder at the images' current midpoints; the analysis head and the z records are done
         once.  An image's record is the one of its smallest successful probe; where none fits, of its last probe,
-        which is q = Q_MAX.  The size is taken to be non-increasing in q."""
+        which is q = Q_MAX.  The size is taken to be non-increasing in q.  qm (MCM._check_qoffsets' pair): q is the
+        base position, the levels are selected once and the map is rebuilt per probe (tmae_qmap_build)."""
         from .bitstream import Q_MAX, Q_MIN
 
         B = self.batch
+        if qm is not None:
+            qm = self._map_upload(qm)
         zsym, rest = self._analysis_head(imgs, scores)
+        if qm is not None:
+            self.last_levels, lstatus = self._select_levels(qm, scores, self.last_ids_shuffle)
         z_strings = self._code_z(zsym, z_lanes)
         lo, hi = [Q_MIN] * B, [Q_MAX + 1] * B
         kept = [None] * B  # (q, y record)
         while any(l < h for l, h in zip(lo, hi)):
             mid = [(l + h) // 2 if l < h else min(l, Q_MAX) for l, h in zip(lo, hi)]  # settled images: any valid q
-            sym, idx = self._analysis_slices(self._q_dev(mid))
+            qd = self._q_dev(mid)
+            sym, idx = self._analysis_slices(qd, None if qm is None else ops.qmap_build(self.last_levels, qd, qm[2]))
             y_strings = self._code_y(sym, idx, lanes)
             for b in range(B):
                 if lo[b] >= hi[b]:
@@ -1185,6 +1381,8 @@ class _Executor:
                     lo[b] = mid[b] + 1
                     if mid[b] == Q_MAX:
                         kept[b] = (Q_MAX, y_strings[b])
+        if qm is not None and lstatus is not None:
+            self._raise_levels(lstatus.cpu().numpy(), "encode_bytes")
         self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # of the last probe
         return z_strings, [k[1] for k in kept], [k[0] for k in kept]
 
@@ -1196,13 +1394,15 @@ class _Executor:
             zidx = self._zidx = torch.from_numpy(zidx).to(self.device)
         return zidx
 
-    def decompress_batch(self, strings, shape, ids_restore, lanes=1, z_lanes=1, ids_status=None, q=None):
+    def decompress_batch(self, strings, shape, ids_restore, lanes=1, z_lanes=1, ids_status=None, q=None, qm=None):
         """decompress of per-image records: every string goes up in one copy, the z and y streams are decoded by
         device kernels (the y streams inside the slice loop, one call per slice step), and nothing synchronises with
         the host until the status words are read after the last kernel of _back has been enqueued.  ids_status
         (decode_bytes): ops.ids_unpack's device status words of ids_restore, read in that same copy.  q: None or B
-        ladder positions (compress_batch's), uploaded before the first launch"""
-        from .bitstream import IDS_STATUS
+        ladder positions (compress_batch's), uploaded before the first launch.  qm: dict of levels
+        int32 [B, K], their device status words or None (read in the same copy) and offsets int32 [B, 16], all on the
+        device; the map is built from them at the base q and the _qm kernels run"""
+        from .bitstream import IDS_STATUS, LEVELS_STATUS
         from .coder import DeviceRansDecoder, _raise_status
 
         m, B = self.m, self.batch
@@ -1216,6 +1416,7 @@ class _Executor:
         zidx = self._z_indexes()
         rest = ids_restore.to(self.device)
         qd = self._q_dev(q)
+        qmap = None if qm is None else ops.qmap_build(qm["levels"], qd, qm["offsets"])
         dec = DeviceRansDecoder()  # records [0, B): y, [B, 2B): z; a bad header raises here, before the first launch
         dec.set_records(list(strings[0]) + list(strings[1]), [lanes] * B + [z_lanes] * B, self.device,
                         what=[f"{c} stream of image {b}" for c in "yz" for b in range(B)])
@@ -1230,12 +1431,17 @@ class _Executor:
         M, dt = m.latent_depth, self.dtype
 
         def step(i0, nbs, mu, sigma, ms_stride):
-            if qd is None:
+            if qmap is not None:
+                ops.gc_indexes_qm(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:], qmap)
+            elif qd is None:
                 ops.gc_indexes(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:])
             else:
                 ops.gc_indexes_q(sigma, ms_stride, sw, B, HW, nbs, sw, gc.scale_table, bound, idx[i0 * per:], qd)
             decode(0, B, idx, (per, sw * HW), sym, (per, sw * HW), i0, nbs, sw * HW, gtabs)
-            if qd is None:
+            if qmap is not None:
+                ops.gc_dequantize_qm(sym[i0 * per:], mu, ms_stride, sw, B, HW, nbs, sw, i0 * sw, self.SUPY, dt, M,
+                                     self.YPRE, M, qmap)
+            elif qd is None:
                 ops.gc_dequantize(sym[i0 * per:], mu, ms_stride, sw, B, HW, nbs, sw, i0 * sw, self.SUPY, dt, M,
                                   self.YPRE, M)
             else:
@@ -1246,10 +1452,22 @@ class _Executor:
         self.last_decoded = _LazyStreams(y_symbols=sym, y_indexes=idx)  # what the decoder saw (diagnostics, tests)
         shuf = ops.invert_permutation(rest)
         x_hat = self._back(shuf, m.encoder_embed.proj.in_channels)
-        status = dec.status(ids_status)  # the only synchronisation: after everything is enqueued
-        for b in np.flatnonzero(status[2 * B:]):
-            c = int(status[2 * B + b])
-            raise ValueError(f"side information of image {int(b)}: {IDS_STATUS.get(c, f'status {c}')}")
+        lstatus = None if qm is None else qm.get("status")
+        extra = [t for t in (ids_status, lstatus) if t is not None]
+        # the only synchronisation: after everything is enqueued
+        status = dec.status(torch.cat([t.reshape(-1) for t in extra]) if extra else None)
+        at = 2 * B
+        if ids_status is not None:
+            for b in np.flatnonzero(status[at:at + B]):
+                c = int(status[at + b])
+                raise ValueError(f"side information of image {int(b)}: {IDS_STATUS.get(c, f'status {c}')}")
+            at += B
+        if lstatus is not None:
+            for b in np.flatnonzero(status[at:at + B]):
+                c = int(status[at + b])
+                if qm.get("who"):
+                    self._raise_levels(status[at:at + B], "decompress_batch")
+                raise ValueError(f"side information of image {int(b)}: {LEVELS_STATUS.get(c, f'status {c}')}")
         _raise_status(status[:B], "y stream of image")
         _raise_status(status[B:2 * B], "z stream of image")
         return x_hat
@@ -1359,13 +1577,17 @@ class _Executor:
     # Each is called with (i0, nbs, mu, sigma, ms_stride): slices i0..i0+nbs-1, mu/sigma device addresses
     # of rows [Mp][sw] per slice, ms_stride elements apart; it must leave y_hat (pre-LRP) in SUPY (operand
     # dtype) and YPRE (f32) at channels i0*sw.. .
-    def _gc_forward(self, y_noise, qd=None):
-        """qd: per-image ladder positions on the device (the kernel at a step) or None"""
+    def _gc_forward(self, y_noise, qd=None, qmap=None):
+        """qd: per-image ladder positions on the device (the kernel at a step) or None; qmap: ladder
+        positions per kept patch, int32 [B, K] (§3.19), which takes precedence"""
         M, sw, B, HW, dt = self.m.latent_depth, self.sw, self.batch, self.g * self.g, self.dtype
         bound = self.scale_bound
 
         def step(i0, nbs, mu, sigma, ms_stride):
-            if qd is None:
+            if qmap is not None:
+                ops.gc_slices_fwd_qm(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, y_noise, self.YLIK, M, self.SUPY,
+                                     dt, M, self.YPRE, M, B, HW, nbs, sw, bound, qmap)
+            elif qd is None:
                 ops.gc_slices(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, y_noise, self.YLIK, M, self.SUPY, dt, M,
                               self.YPRE, M, B, HW, nbs, sw)
             else:
@@ -1373,7 +1595,7 @@ class _Executor:
                                     dt, M, self.YPRE, M, B, HW, nbs, sw, bound, qd)
         return step
 
-    def _gc_compress(self, sym, idx, qd=None):
+    def _gc_compress(self, sym, idx, qd=None, qmap=None):
         """eval step + int32 symbols / scale indexes in the coder's [slice][image][channel][pixel] order; qd: per-image
         ladder positions on the device (the _q kernel, which skips the likelihoods nobody reads here) or None"""
         gc = self.m.gaussian_conditional
@@ -1383,7 +1605,10 @@ class _Executor:
         per = B * sw * HW
 
         def step(i0, nbs, mu, sigma, ms_stride):
-            if qd is None:
+            if qmap is not None:
+                ops.gc_slices_code_qm(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, None, M, self.SUPY, dt, M,
+                                      self.YPRE, M, B, HW, nbs, sw, sym[i0 * per:], idx[i0 * per:], table, bound, qmap)
+            elif qd is None:
                 ops.gc_slices_code(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, self.YLIK, M, self.SUPY, dt, M,
                                    self.YPRE, M, B, HW, nbs, sw, sym[i0 * per:], idx[i0 * per:], table)
             else:

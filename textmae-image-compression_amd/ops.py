@@ -20,6 +20,8 @@ __all__ = [
     "mask_rows", "decoder_pred", "conv3x3", "lic_stack", "pack_lic_stack_weight", "lic_stack_fits", "gc_slices", "eb_likelihood", "eb_aux_loss",
     "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "mha_plan", "mha_force_stream", "dtype_code", "gc_slices_code", "gc_indexes",
     "gc_dequantize", "gc_slices_fwd_q", "gc_slices_code_q", "gc_indexes_q", "gc_dequantize_q",
+    "gc_slices_fwd_qm", "gc_slices_code_qm", "gc_indexes_qm", "gc_dequantize_qm",
+    "qlevels_select", "qlevels_pack", "qlevels_unpack", "qmap_build",
     "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
     "rans_encode_lanes", "rans_decode_lanes", "ids_pack", "ids_unpack",
@@ -530,6 +532,119 @@ def gc_dequantize_q(symbols, mu, ms_stride, ld_ms, n, HW, nslices, sw, yoff, yha
                     q):
     _lib.call("tmae_gc_dequantize_q", _p(symbols), _p(mu), ms_stride, ld_ms, n, HW, nslices, sw, yoff, _p(yhat),
               dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, _q_ptr(q, n), _stream())
+
+
+def _qmap_ptr(qmap, n, HW):
+    """device address of the per-pixel ladder positions (int32 [n, HW], required)"""
+    if qmap is None:
+        raise ValueError("qmap is required (int32 [n, HW] on the device)")
+    _need(qmap, torch.int32, "qmap")
+    if qmap.numel() != n * HW:
+        raise ValueError(f"qmap holds {qmap.numel()} entries for {n} images of {HW} pixels")
+    return qmap.data_ptr()
+
+
+def gc_slices_code_qm(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, lik, Mtot, yhat, yhat_dtype, ld_yhat, yhat32, ld32, n,
+                      HW, nslices, sw, symbols, indexes, scale_table, scale_bound, qmap):
+    """gc_slices_code_q with the quantiser step per pixel of the latent grid, i.e. per kept patch:
+    qmap int32 [n, HW] on the device, the clamped ladder positions of qmap_build; lik may be None"""
+    st = _need(scale_table.contiguous(), torch.float32, "scale_table")
+    _lib.call("tmae_gc_slices_code_qm", _p(y), ldy, yoff, _p(mu), _p(sigma), ms_stride, ld_ms, _p(lik), Mtot, _p(yhat),
+              dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, n, HW, nslices, sw, _p(symbols), _p(indexes),
+              st.data_ptr(), st.numel(), float(scale_bound), _qmap_ptr(qmap, n, HW), _stream())
+
+
+def gc_slices_fwd_qm(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, noise, lik, Mtot, yhat, yhat_dtype, ld_yhat, yhat32,
+                     ld32, n, HW, nslices, sw, scale_bound, qmap):
+    """gc_slices_fwd_q at a step per pixel (qmap int32 [n, HW]); without noise bitwise gc_slices_code_qm's y_hat and
+    likelihood"""
+    _lib.call("tmae_gc_slices_fwd_qm", _p(y), ldy, yoff, _p(mu), _p(sigma), ms_stride, ld_ms, _p(noise), _p(lik), Mtot,
+              _p(yhat), dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, n, HW, nslices, sw, float(scale_bound),
+              _qmap_ptr(qmap, n, HW), _stream())
+
+
+def gc_indexes_qm(sigma, ms_stride, ld_ms, n, HW, nslices, sw, scale_table, scale_bound, indexes, qmap):
+    st = _need(scale_table.contiguous(), torch.float32, "scale_table")
+    _lib.call("tmae_gc_indexes_qm", _p(sigma), ms_stride, ld_ms, n, HW, nslices, sw, st.data_ptr(), st.numel(),
+              float(scale_bound), _p(indexes), _qmap_ptr(qmap, n, HW), _stream())
+
+
+def gc_dequantize_qm(symbols, mu, ms_stride, ld_ms, n, HW, nslices, sw, yoff, yhat, yhat_dtype, ld_yhat, yhat32, ld32,
+                     qmap):
+    _lib.call("tmae_gc_dequantize_qm", _p(symbols), _p(mu), ms_stride, ld_ms, n, HW, nslices, sw, yoff, _p(yhat),
+              dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, _qmap_ptr(qmap, n, HW), _stream())
+
+
+def _check_nlev(nlev, who):
+    nlev = int(nlev)
+    if not 2 <= nlev <= 16:
+        raise ValueError(f"{who}: nlev = {nlev} outside 2..16")
+    return nlev
+
+
+def qlevels_select(ids_shuffle, K: int, nlev: int, scores=None, level_map=None):
+    """the level of every kept patch (bitstream.select_levels_host on the device) -> (levels int32
+    [n, K], status int32 [n]).  Exactly one source: scores f32 [n, L] (rank of the kept patch's score among the kept
+    patches' scores, level 0 the highest share) or level_map int32 [n, L] in image patch order, gathered by
+    ids_shuffle int64 [n, L]; status 1 = a gathered map entry outside 0..nlev-1, that image's levels all zero"""
+    s = _need(ids_shuffle, torch.int64, "ids_shuffle")
+    n, L = s.shape
+    nlev = _check_nlev(nlev, "qlevels_select")
+    if not 1 <= K <= L:
+        raise ValueError(f"qlevels_select: need 1 <= K={K} <= L={L}")
+    if (scores is None) == (level_map is None):
+        raise ValueError("qlevels_select: give scores or level_map, exactly one")
+    src = _need(scores, torch.float32, "scores") if level_map is None else _need(level_map, torch.int32, "level_map")
+    if tuple(src.shape) != (n, L):
+        raise ValueError(f"qlevels_select: the source must be [{n}, {L}], got {tuple(src.shape)}")
+    levels = torch.empty((n, int(K)), dtype=torch.int32, device=s.device)
+    status = torch.empty(n, dtype=torch.int32, device=s.device)
+    _lib.call("tmae_qlevels_select", _p(scores), _p(level_map), s.data_ptr(), levels.data_ptr(), status.data_ptr(), n,
+              L, int(K), nlev, _stream())
+    return levels, status
+
+
+def qlevels_pack(levels, nlev: int):
+    """levels int32 [n, K] -> int32 [n, bitstream.level_words(K, nlev)] holding the container's little-endian words
+    (bitstream.pack_levels_host on the device)"""
+    from .bitstream import level_words
+
+    lv = _need(levels, torch.int32, "levels")
+    nlev = _check_nlev(nlev, "qlevels_pack")
+    n, K = lv.shape
+    words = torch.empty((n, level_words(K, nlev)), dtype=torch.int32, device=lv.device)
+    _lib.call("tmae_qlevels_pack", lv.data_ptr(), words.data_ptr(), n, K, nlev, _stream())
+    return words
+
+
+def qlevels_unpack(words, nlev, K: int):
+    """words int32 [n, ldw] (rows padded to a common width) and the table size of every image, nlev int32 [n] on the
+    device (1 = the image has no map: nothing is read) -> (levels int32 [n, K], status int32 [n]): 0 ok, 1 a level >=
+    nlev, 2 non-zero tail bits; an image with a fault gets all-zero levels.  Nothing synchronises."""
+    w = _need(words, torch.int32, "words")
+    nl = _need(nlev, torch.int32, "nlev")
+    if w.dim() != 2 or nl.dim() != 1 or nl.numel() != w.shape[0]:
+        raise ValueError(f"qlevels_unpack: words must be [n, ldw] and nlev [n], got {tuple(w.shape)} and "
+                         f"{tuple(nl.shape)}")
+    n, ldw = w.shape
+    levels = torch.empty((n, int(K)), dtype=torch.int32, device=w.device)
+    status = torch.empty(n, dtype=torch.int32, device=w.device)
+    _lib.call("tmae_qlevels_unpack", w.data_ptr() if ldw else None, ldw, nl.data_ptr(), levels.data_ptr(),
+              status.data_ptr(), n, int(K), _stream())
+    return levels, status
+
+
+def qmap_build(levels, q, offsets):
+    """qmap[b][p] = clamp(q[b] + offsets[b][levels[b][p]], -32, 32) -> int32 [n, K] (bitstream.build_qmap_host on the
+    device); levels int32 [n, K], q int32 [n] or None (all zero), offsets int32 [n, 16]"""
+    lv = _need(levels, torch.int32, "levels")
+    off = _need(offsets, torch.int32, "offsets")
+    n, K = lv.shape
+    if tuple(off.shape) != (n, 16):
+        raise ValueError(f"qmap_build: offsets must be [{n}, 16], got {tuple(off.shape)}")
+    qmap = torch.empty_like(lv)
+    _lib.call("tmae_qmap_build", lv.data_ptr(), _q_ptr(q, n), off.data_ptr(), qmap.data_ptr(), n, K, _stream())
+    return qmap
 
 
 def gc_pmf(scale_table, pmf_center, max_length):

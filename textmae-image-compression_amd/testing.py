@@ -114,11 +114,12 @@ def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None,
 
 @torch.no_grad()
 def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_dir, output_dir=None, lanes=None,
-                        original_size=False, q=None):
+                        original_size=False, q=None, qoffsets=None):
     """--bitstream DIR: encode_bytes -> DIR/<name>.tmc -> read the file back -> decode_bytes.  The bpp is that of
     the file, 8 * size / pixels: header and side information counted in full.  original_size takes the size the
     blob itself recorded.  q (--q N): the y quantiser step's ladder position (MCM.encode_bytes), read back from the
-    file by decode_bytes."""
+    file by decode_bytes.  qoffsets (--q-offsets): a step per kept patch, recorded in the file
+    too."""
     device = next(model.parameters()).device
     x = x.to(device)
     total_score = total_score.to(device)
@@ -126,7 +127,7 @@ def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_d
     torch.cuda.synchronize()
     start = time.time()
     blobs = model.encode_bytes(x, total_score, lanes=1 if lanes is None else lanes,
-                               orig_sizes=[(int(ori_shape[0]), int(ori_shape[1]))], q=q)
+                               orig_sizes=[(int(ori_shape[0]), int(ori_shape[1]))], q=q, qoffsets=qoffsets)
     enc_time = time.time() - start
     with open(path, "wb") as f:
         f.write(blobs[0])
@@ -149,7 +150,7 @@ MS_SSIM_MIN_SIDE = 161  # five scales of an 11-tap window: the smaller side must
 
 @torch.no_grad()
 def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, output_dir=None, lanes=None, tile_batch=16,
-                    q=None):
+                    q=None, qoffsets=None):
     """--tiled: the image at its own resolution, rgb uint8 [H, W, 3] -> MCM.encode_image -> (with bitstream_dir)
     DIR/<name>.tmt, read back -> MCM.decode_image.  PSNR / MS-SSIM against the original pixels at that resolution,
     bpp = 8 * file size / (W * H).  An image too small for MS-SSIM's five scales gets PSNR only (no "ms-ssim")."""
@@ -160,7 +161,8 @@ def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, outpu
     H, W = int(x.shape[0]), int(x.shape[1])
     torch.cuda.synchronize()
     start = time.time()
-    blob = model.encode_image(x, overlap=overlap, lanes=1 if lanes is None else lanes, tile_batch=tile_batch, q=q)
+    blob = model.encode_image(x, overlap=overlap, lanes=1 if lanes is None else lanes, tile_batch=tile_batch, q=q,
+                              qoffsets=qoffsets)
     enc_time = time.time() - start
     if bitstream_dir is not None:
         path = os.path.join(bitstream_dir, Path(file_name).stem + ".tmt")
@@ -188,7 +190,8 @@ def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, outpu
     return rv
 
 
-def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_dir=None, tile_batch=16, q=None):
+def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_dir=None, tile_batch=16, q=None,
+               qoffsets=None):
     """--tiled counterpart of eval_model over image files: every metric averaged over the images that have it
     -> (metrics, number of images with MS-SSIM)"""
     from PIL import Image
@@ -199,7 +202,7 @@ def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_d
     sums, counts = defaultdict(float), defaultdict(int)
     for p in filepaths:
         rv = inference_tiled(model, np.array(Image.open(p).convert("RGB")), p.name, overlap, bitstream_dir, output_dir,
-                             lanes, tile_batch, q)
+                             lanes, tile_batch, q, qoffsets)
         for k, v in rv.items():
             sums[k] += v
             counts[k] += 1
@@ -207,14 +210,16 @@ def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_d
 
 
 @torch.no_grad()
-def inference_entropy_estimation(model, x, total_score, q=None):
+def inference_entropy_estimation(model, x, total_score, q=None, qoffsets=None):
     """testing.py:103-120 with the scores passed (the reference omits them and raises).  q (--q N): the estimate at
-    the y quantiser step 2^(N/8) (MCM.forward's q)"""
+    the y quantiser step 2^(N/8) (MCM.forward's q); qoffsets (--q-offsets): at a step per kept patch
+    (§3.19)"""
     device = next(model.parameters()).device
     x, total_score = x.to(device), total_score.to(device)
     torch.cuda.synchronize()
     start = time.time()
-    out = model.forward(x, total_score) if q is None else model.forward(x, total_score, q=q)
+    kw = {k: v for k, v in (("q", q), ("qoffsets", qoffsets)) if v is not None}
+    out = model.forward(x, total_score, **kw)
     torch.cuda.synchronize()
     elapsed = time.time() - start
     metrics = compute_metrics(x, out["x_hat"], 255)
@@ -244,7 +249,7 @@ def load_test_images(paths, size=224, device=None):
 
 
 def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False, lanes=None,
-               original_size=False, bitstream_dir=None, q=None):
+               original_size=False, bitstream_dir=None, q=None, qoffsets=None):
     """testing.py:128-165 over pre-loaded (img [1,3,S,S], orig_shape) pairs and a [N, L] score tensor; with
     bitstream_dir every image goes through its .tmc file there (inference_bitstream; needs names)"""
     metrics = defaultdict(float)
@@ -257,10 +262,10 @@ def eval_model(model, output_dir, images, scores, names=None, entropy_estimation
     for i, (img, ori_shape) in enumerate(images):
         ts = scores[i:i + 1]
         if entropy_estimation:
-            rv = inference_entropy_estimation(model, img, ts, q=q)
+            rv = inference_entropy_estimation(model, img, ts, q=q, qoffsets=qoffsets)
         elif bitstream_dir is not None:
             rv = inference_bitstream(model, img, ori_shape, ts, names[i], bitstream_dir, output_dir, lanes=lanes,
-                                     original_size=original_size, q=q)
+                                     original_size=original_size, q=q, qoffsets=qoffsets)
         else:
             rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir, lanes=lanes,
                            original_size=original_size)
@@ -313,11 +318,26 @@ def setup_args():
                    help="quantiser step 2^(N/8) on the y latents, N in -32..32 (--bitstream / --tiled: DESIGN.md "
                         "§3.17; --entropy-estimation: the estimated rate and x_hat at that step, §3.18): larger N, "
                         "smaller files")
+    p.add_argument("--q-offsets", type=_q_offsets, default=None, metavar="A,B,C,...", dest="q_offsets",
+                   help="a quantiser step per kept patch (DESIGN.md §3.19): 2..16 ladder offsets in -64..64, the first "
+                        "for the most text-like share of the kept patches, added to --q (default 0); with "
+                        "--bitstream / --tiled / --entropy-estimation")
     return p
 
 
+def _q_offsets(text):
+    from .bitstream import check_offsets
+
+    try:
+        return check_offsets([int(v) for v in text.split(",")], "--q-offsets")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def main(argv):
-    args = setup_args().parse_args(argv)
+    from .codec import join_q_offsets
+
+    args = setup_args().parse_args(join_q_offsets(argv))
     filepaths = collect_images(args.dataset)
     if not filepaths:
         print("Error: no images found in directory.", file=sys.stderr)
@@ -328,6 +348,10 @@ def main(argv):
     if args.q is not None and not (args.tiled or args.bitstream is not None or args.entropy_estimation):
         print("Error: --q needs --bitstream DIR or --tiled (real files) or --entropy-estimation (the estimate).",
               file=sys.stderr)
+        sys.exit(1)
+    if args.q_offsets is not None and not (args.tiled or args.bitstream is not None or args.entropy_estimation):
+        print("Error: --q-offsets needs --bitstream DIR or --tiled (real files) or --entropy-estimation (the "
+              "estimate).", file=sys.stderr)
         sys.exit(1)
     if not args.tiled:
         ds = Path(args.dataset)
@@ -348,11 +372,11 @@ def main(argv):
         model.update(force=True)
         if args.tiled:
             m, with_msssim = eval_tiled(model, args.output_path, filepaths, args.overlap, lanes=args.lanes,
-                                        bitstream_dir=args.bitstream, q=args.q)
+                                        bitstream_dir=args.bitstream, q=args.q, qoffsets=args.q_offsets)
         else:
             m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths],
                            args.entropy_estimation, lanes=args.lanes, original_size=args.original_size,
-                           bitstream_dir=args.bitstream, q=args.q)
+                           bitstream_dir=args.bitstream, q=args.q, qoffsets=args.q_offsets)
         for k, v in m.items():
             results[k].append(v)
     desc = "entropy estimation" if args.entropy_estimation else args.entropy_coder
@@ -364,6 +388,8 @@ def main(argv):
         desc += "; bpp of the .tmc files: header and side information counted in full"
     if args.q:
         desc += f"; y quantiser step 2^({args.q}/8)"
+    if args.q_offsets is not None:
+        desc += f"; per-patch ladder offsets {','.join(str(v) for v in args.q_offsets)} by score rank"
     output = {"name": "MCM", "description": f"Inference ({desc})", "results": results}
     print(json.dumps(output, indent=2))
     os.makedirs(args.output_path, exist_ok=True)

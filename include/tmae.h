@@ -202,6 +202,12 @@ typedef struct tmae_lic_stack_args {
    * arithmetic of tmae_gc_slices_fwd_q bit for bit (its own kernel instantiation: NULL runs the code it ran before
    * the field existed).  Rejected with TMAE_LIC_STACK_BWD or without TMAE_LIC_STACK_CHAIN. */
   const int* cq;
+  /* TMAE_LIC_STACK_CHAIN at a quantiser step per pixel of the latent grid, i.e. per kept patch: device
+   * int32 [n][npix] clamped ladder positions (what tmae_qmap_build writes), or NULL.  The chain then builds y_hat_pre
+   * as above with delta = delta(cqm[image * npix + pixel]), the arithmetic of tmae_gc_slices_fwd_qm bit for bit; a map
+   * that is constant over an image gives cq's bits.  Its own kernel instantiation (lic_stack_qm.hip).  Rejected
+   * together with cq, with TMAE_LIC_STACK_BWD, or without TMAE_LIC_STACK_CHAIN. */
+  const int* cqm;
 } tmae_lic_stack_args;
 #define TMAE_LIC_STACK_CHAIN 1
 /* TMAE_LIC_STACK_BWD (training backward, mcm_train.py): the stack's data-gradient chain through LDS.  x1 = the
@@ -722,6 +728,13 @@ int tmae_gc_bwd(const float* y, int ldy, int yoff, const float* mu, const float*
 int tmae_gc_bwd_q(const float* y, int ldy, int yoff, const float* mu, const float* sigma, int ld_ms, const float* noise,
                   int Mtot, const float* glik, const float* gyp, int ldg, float* dy, int lddy, void* dmu, void* dsigma,
                   int ldd, int n, int HW, int sw, int dtype, float scale_bound, const int* q, void* stream);
+/* The backward of tmae_gc_slices_fwd_qm for one slice: tmae_gc_bwd_q with the step per pixel of the
+ * latent grid, delta = delta(qmap[image * HW + pixel]); qmap device int32 [n][HW], required (the clamped ladder
+ * positions of tmae_qmap_build).  Every rule above holds element by element at the element's own step; with
+ * qmap[b][.] = q[b] every output is bitwise tmae_gc_bwd_q's. */
+int tmae_gc_bwd_qm(const float* y, int ldy, int yoff, const float* mu, const float* sigma, int ld_ms, const float* noise,
+                   int Mtot, const float* glik, const float* gyp, int ldg, float* dy, int lddy, void* dmu, void* dsigma,
+                   int ldd, int n, int HW, int sw, int dtype, float scale_bound, const int* qmap, void* stream);
 /* EntropyBottleneck likelihood backward (MCM.py:741-744): dz NHWC (= gzhat pass-through + likelihood path) and
  * every density parameter's gradient into `grads` (same struct, f32 gradient buffers; =/+=) */
 int tmae_eb_bwd(const tmae_eb_params* params, const float* z, const float* noise, const float* glik,

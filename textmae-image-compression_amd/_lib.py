@@ -98,6 +98,7 @@ class LicStackArgs(ctypes.Structure):
         ("csv_t", P), ("cs_t", LL),
         ("racc", P * 3), ("rld", I * 3), ("rlim", I * 3), ("rs", LL * 3),
         ("cq", P),
+        ("cqm", P),
     ]
 
 
@@ -230,6 +231,7 @@ SIGNATURES = {
     "tmae_copy2d": [P, I, P, I, I, I, I, P],
     "tmae_gc_bwd": [P, I, I, P, P, I, P, I, P, P, I, P, I, P, P, I, I, I, I, I, P],
     "tmae_gc_bwd_q": [P, I, I, P, P, I, P, I, P, P, I, P, I, P, P, I, I, I, I, I, F, P, P],
+    "tmae_gc_bwd_qm": [P, I, I, P, P, I, P, I, P, P, I, P, I, P, P, I, I, I, I, I, F, P, P],
     "tmae_eb_bwd": [ctypes.POINTER(EBParams), P, P, P, P, P, I, I, I, ctypes.POINTER(EBParams), I, P],
     "tmae_eb_aux_bwd": [ctypes.POINTER(EBParams), P, P, P, I, I, P],
     "tmae_bpp_bwd": [P, P, P, LL, ctypes.c_double, P],

@@ -26,8 +26,9 @@
 // the last layer's writes mu / sigma (f32) or, for lrp, y_hat = y_hat_pre + 0.5 tanh(.) (MCM.py:779-784).
 #include "lic_stack_kernel.h"
 
-// the QSTEP instantiation and its launch (lic_stack_q.hip)
+// the QSTEP instantiations and their launches (lic_stack_q.hip: a step per image, lic_stack_qm.hip: a step per pixel)
 int lic_stack_launch_q(const tmae_lic_stack_args& a, int nwg, hipStream_t stream);
+int lic_stack_launch_qm(const tmae_lic_stack_args& a, int nwg, hipStream_t stream);
 
 extern "C" int tmae_lic_stack(const tmae_lic_stack_args* args, void* stream) {
   using namespace lstk;
@@ -39,6 +40,10 @@ extern "C" int tmae_lic_stack(const tmae_lic_stack_args* args, void* stream) {
   const bool bwd = (a.flags & TMAE_LIC_STACK_BWD) != 0;
   TMAE_REQUIRE(!a.cq || (!bwd && (a.flags & TMAE_LIC_STACK_CHAIN)),
                "tmae_lic_stack: cq (the chain's quantiser step) needs TMAE_LIC_STACK_CHAIN and no TMAE_LIC_STACK_BWD");
+  TMAE_REQUIRE(!a.cqm || !a.cq, "tmae_lic_stack: cqm (a step per pixel) and cq (a step per image) exclude each other");
+  TMAE_REQUIRE(!a.cqm || !bwd, "tmae_lic_stack: cqm (the chain's quantiser steps per pixel) takes no TMAE_LIC_STACK_BWD");
+  TMAE_REQUIRE(!a.cqm || (a.flags & TMAE_LIC_STACK_CHAIN),
+               "tmae_lic_stack: cqm (the chain's quantiser steps per pixel) needs TMAE_LIC_STACK_CHAIN");
   TMAE_REQUIRE(a.x1 != nullptr && (a.y != nullptr || bwd), "tmae_lic_stack: x1 / y required");
   if (bwd) {
     TMAE_REQUIRE(!(a.flags & TMAE_LIC_STACK_CHAIN) && !a.addend && !a.lrp_src && !a.x2 && !a.sv_t,
@@ -90,9 +95,10 @@ extern "C" int tmae_lic_stack(const tmae_lic_stack_args* args, void* stream) {
     TMAE_REQUIRE(!a.csv_pre[l] == !a.csv_act[l], "tmae_lic_stack: chain layer %d keeps pre and output together", l);
   TMAE_REQUIRE(!a.sv_t || a.lrp_src, "tmae_lic_stack: sv_t is the lrp stack's pre-tanh value");
   const int nwg = a.n * a.nb1 * a.nb2;
-  if (bwd) hipLaunchKernelGGL((lic_stack_kernel<true, false>), dim3(nwg), dim3(NW * 64), 0, (hipStream_t)stream, a);
+  if (bwd) hipLaunchKernelGGL((lic_stack_kernel<true, 0>), dim3(nwg), dim3(NW * 64), 0, (hipStream_t)stream, a);
   else if (a.cq) return lic_stack_launch_q(a, nwg, (hipStream_t)stream);
-  else hipLaunchKernelGGL((lic_stack_kernel<false, false>), dim3(nwg), dim3(NW * 64), 0, (hipStream_t)stream, a);
+  else if (a.cqm) return lic_stack_launch_qm(a, nwg, (hipStream_t)stream);
+  else hipLaunchKernelGGL((lic_stack_kernel<false, 0>), dim3(nwg), dim3(NW * 64), 0, (hipStream_t)stream, a);
   TMAE_LAUNCH_CHECK("tmae_lic_stack");
 }
 

@@ -1,8 +1,9 @@
 // tmae_lic_stack's kernel (lic_stack.hip has the description): constants, the wave item and the kernel template.  A
-// header because the kernel's instantiations are compiled in two translation units: lic_stack.hip has the forward and
-// the backward one, lic_stack_q.hip the forward at a quantiser step (QSTEP).  Compiled next to the other two, the third
-// changed the forward's register allocation and schedule (6196 differing runs of its 188k instructions, same register
-// counts); alone, the two compile to the instructions they had before QSTEP existed.
+// header because the kernel's instantiations are compiled in three translation units: lic_stack.hip has the forward and
+// the backward one, lic_stack_q.hip the forward at a quantiser step per image (QSTEP = 1), lic_stack_qm.hip the forward
+// at a step per pixel (QSTEP = 2).  Compiled next to the other two, the third changed the forward's register allocation
+// and schedule (6196 differing runs of its 188k instructions, same register counts); alone, the two compile to the
+// instructions they had before QSTEP existed.  The fourth follows the third for the same reason.
 #pragma once
 #include "gemm_core.h"
 #include "gc_q.h"
@@ -381,9 +382,10 @@ __device__ __forceinline__ void lstk_dispatch(int nkc, const LstkLayer& L, bool 
 
 
 // BWD (TMAE_LIC_STACK_BWD) is its own instantiation: the backward epilogue's registers stay out of the forward's.
-// QSTEP (cq set) is one too: the chain builds y_hat_pre at the image's quantiser step; the step's
+// QSTEP = 1 (cq set) is one too: the chain builds y_hat_pre at the image's quantiser step; the step's
 // registers and its division stay out of the two instantiations above, which compile to what they did without it.
-template <bool BWD, bool QSTEP>
+// QSTEP = 2 (cqm set): the step of every pixel comes from a map.
+template <bool BWD, int QSTEP>
 __global__ void __launch_bounds__(lstk::NW * 64) lic_stack_kernel(tmae_lic_stack_args) {
   using namespace lstk;
   LstkArgs* a = (LstkArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -469,7 +471,9 @@ __global__ void __launch_bounds__(lstk::NW * 64) lic_stack_kernel(tmae_lic_stack
       float* ypre = a->csrc + b2 * a->cs_src;
       const int cld1 = a->cld1, ldyv = a->ldyv, ldp = a->cld_src;
       float delta = 1.0f;  // uniform over the workgroup (one image)
-      if constexpr (QSTEP) delta = tmae_qstep(a->cq[img]);
+      if constexpr (QSTEP == 1) delta = tmae_qstep(a->cq[img]);
+      const int* qmap = nullptr;  // QSTEP = 2: this image's row of the map, one clamped ladder position per pixel
+      if constexpr (QSTEP == 2) qmap = a->cqm + (size_t)img * npix;
       cin = cc1 + sw;
       const int q = pad32(cin) >> 3, pin = pitch(cin);
       for (int i = tid; i < npix * q; i += NW * 64) {
@@ -483,9 +487,10 @@ __global__ void __launch_bounds__(lstk::NW * 64) lic_stack_kernel(tmae_lic_stack
           f32x4 y0, y1, m0, m1;
           load8f(yv + row * ldyv + c, y0, y1);
           load8f(mu + row * ldmu + c, m0, m1);
+          if constexpr (QSTEP == 2) delta = tmae_qstep(qmap[p]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            if constexpr (QSTEP) {  // the coder's arithmetic (gc_q.h), bit for bit tmae_gc_slices_fwd_q's y_hat
+            if constexpr (QSTEP != 0) {  // the coder's arithmetic (gc_q.h), bit for bit tmae_gc_slices_fwd_q's y_hat
               y0[e] = gcq_recon(rintf(gcq_scaled(y0[e], m0[e], delta)), m0[e], delta);
               y1[e] = gcq_recon(rintf(gcq_scaled(y1[e], m1[e], delta)), m1[e], delta);
             } else {

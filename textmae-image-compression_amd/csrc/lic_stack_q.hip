@@ -6,6 +6,6 @@
 #include "lic_stack_kernel.h"
 
 int lic_stack_launch_q(const tmae_lic_stack_args& a, int nwg, hipStream_t stream) {
-  hipLaunchKernelGGL((lic_stack_kernel<false, true>), dim3(nwg), dim3(lstk::NW * 64), 0, stream, a);
+  hipLaunchKernelGGL((lic_stack_kernel<false, 1>), dim3(nwg), dim3(lstk::NW * 64), 0, stream, a);
   TMAE_LAUNCH_CHECK("tmae_lic_stack");
 }

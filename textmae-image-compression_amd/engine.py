@@ -41,16 +41,24 @@ METRICS = ("loss", "L1_loss", "ssim_loss", "vgg_loss", "bpp_loss", "aux_loss")
 
 
 def train_step(model, criterion, samples, total_scores, optimizer, aux_optimizer, clip_max_norm=1.0, accum_iter=1,
-               step_now=True, noise=None, q=None, lmbda=None):
+               step_now=True, noise=None, q=None, lmbda=None, qoffsets=None, qlevels=None, _qmap_kw=None):
     """one iteration of the reference loop body (utils/engine.py:72-91); returns the device losses.  q: the y
     quantiser step of this iteration (MCM.forward's q: an int, one per image, or an int32 device tensor), lmbda: the
-    criterion's weight for it (RateDistortionLoss.forward's lmbda, e.g. rd_loss.lmbda_for_q)"""
+    criterion's weight for it (RateDistortionLoss.forward's lmbda, e.g. rd_loss.lmbda_for_q).  qoffsets / qlevels
+    (DESIGN.md §3.20): a table of ladder offsets and the source of the per-patch levels ("scores", the default, or a
+    map); the step then runs MCM.forward_qmap, q being the base position"""
     kw = {}
     if noise is not None:
         kw["noise"] = noise
     if q is not None:
         kw["q"] = q
-    out_net = model(samples, total_scores, **kw)
+    if qoffsets is None:
+        if qlevels is not None:
+            raise ValueError("train_step: qlevels without qoffsets (the table the levels index)")
+        out_net = model(samples, total_scores, **kw)
+    else:
+        out_net = model.forward_qmap(samples, total_scores, qoffsets=qoffsets,
+                                     qlevels="scores" if qlevels is None else qlevels, **kw, **(_qmap_kw or {}))
     out_criterion = criterion(out_net, samples) if lmbda is None else criterion(out_net, samples, lmbda=lmbda)
     out_criterion["loss"] = out_criterion["loss"] / accum_iter
     aux_loss = model.aux_loss() / accum_iter
@@ -103,10 +111,18 @@ class GraphedTrainStep:
     q / lmbda, given at capture: the y quantiser step of the captured step (an int or one per
     image) and the criterion's weight live in a static int32 [B] and a static 0-d f32 device buffer that every call
     refreshes, so both may change from replay to replay without a new capture: the captured forward and backward
-    always run the kernels with a step, at q = 0 too."""
+    always run the kernels with a step, at q = 0 too.
+
+    qoffsets / qlevels, given at capture: the step runs MCM.forward_qmap.  The table lives in a
+    static int32 [B, 16] device buffer that every call refreshes, so its values may change from replay to replay; its
+    size is fixed at capture (the level rule depends on it) and a table of another size raises.  With qlevels =
+    "scores" (the default) the selection and the map's construction are kernels of the captured step.  With a device
+    map of levels (int32 [B, L], image patch order) the step keeps a static [B, L] buffer refreshed per call; the
+    map's status is not read during a replay: ``step.qlevels_status`` (int32 [B], 1 = an entry outside the table) is
+    the caller's to read, and an image with such an entry trains at all-zero levels, as the kernel defines."""
 
     def __init__(self, model, criterion, optimizer, aux_optimizer, samples, total_scores, clip_max_norm=1.0,
-                 warmup=1, noise=None, q=None, lmbda=None):
+                 warmup=1, noise=None, q=None, lmbda=None, qoffsets=None, qlevels=None):
         sync = getattr(model, "grad_sync", None)
         if sync is not None and not sync.capturable():
             raise ValueError("GraphedTrainStep: a gloo gradient all-reduce (host-staged) is not capturable; use "
@@ -124,9 +140,58 @@ class GraphedTrainStep:
         self.q = None if q is None else torch.empty(samples.shape[0], dtype=torch.int32, device=dev)
         self.lmbda = None if lmbda is None else torch.empty((), dtype=torch.float32, device=dev)
         self._refresh_q(q, lmbda)
+        B = samples.shape[0]
+        self.qoffsets = self.qlevels = self.nlev = None
+        if qoffsets is None:
+            if qlevels is not None:
+                raise ValueError("GraphedTrainStep: qlevels without qoffsets (the table the levels index)")
+        else:
+            from .bitstream import check_offsets
+
+            self.nlev = len(check_offsets(qoffsets, "GraphedTrainStep: qoffsets"))
+            self.qoffsets = torch.zeros((B, 16), dtype=torch.int32, device=dev)
+            if qlevels is not None and not isinstance(qlevels, str):
+                if not (torch.is_tensor(qlevels) and qlevels.is_cuda and qlevels.dtype == torch.int32
+                        and qlevels.dim() == 2 and qlevels.shape[0] == B):
+                    raise ValueError("GraphedTrainStep: qlevels must be 'scores' or an int32 [B, L] device tensor")
+                self.qlevels = torch.empty_like(qlevels, memory_format=torch.contiguous_format)
+            elif qlevels not in (None, "scores"):
+                raise ValueError(f"GraphedTrainStep: qlevels = {qlevels!r}: 'scores' or an int32 [B, L] device tensor")
+        self._refresh_qmap(qoffsets, qlevels)
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.graph, self.out = None, None
         self._capture(warmup)
+
+    @property
+    def qlevels_status(self):
+        """the last step's status of a device map of levels (int32 [B] on the device; None without such a map)"""
+        ex = getattr(self.model, "_train_exec", None)
+        return None if self.qlevels is None or ex is None else ex.qm_status
+
+    def _refresh_qmap(self, qoffsets, qlevels):
+        """copy this call's table (and device map of levels) into the static buffers"""
+        if (qoffsets is None) != (self.qoffsets is None):
+            raise ValueError("GraphedTrainStep: qoffsets must be given at every call iff it was given at capture")
+        if qoffsets is None:
+            if qlevels is not None:
+                raise ValueError("GraphedTrainStep: qlevels without qoffsets (the table the levels index)")
+            return
+        from .bitstream import check_offsets, offsets_row
+
+        offs = check_offsets(qoffsets, "GraphedTrainStep: qoffsets")
+        if len(offs) != self.nlev:
+            raise ValueError(f"GraphedTrainStep: a table of {len(offs)} offsets at a step captured with {self.nlev}: "
+                             "the table size is fixed at capture")
+        self._offs = offs
+        self.qoffsets.copy_(torch.tensor([offsets_row(offs)] * self.qoffsets.shape[0], dtype=torch.int32),
+                            non_blocking=True)
+        given = qlevels is not None and not isinstance(qlevels, str)
+        if given != (self.qlevels is not None):
+            raise ValueError("GraphedTrainStep: a map of levels must be given at every call iff it was given at capture")
+        if given:
+            if not torch.is_tensor(qlevels) or qlevels.dtype != torch.int32 or qlevels.shape != self.qlevels.shape:
+                raise ValueError(f"GraphedTrainStep: qlevels must be int32 {tuple(self.qlevels.shape)}")
+            self.qlevels.copy_(qlevels, non_blocking=True)
 
     def _hyper(self):
         return tuple((g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"])
@@ -156,7 +221,16 @@ class GraphedTrainStep:
 
     def _step(self):
         return train_step(self.model, self.criterion, self.samples, self.total_scores, self.optimizer,
-                          self.aux_optimizer, self.clip_max_norm, noise=self.noise, q=self.q, lmbda=self.lmbda)
+                          self.aux_optimizer, self.clip_max_norm, noise=self.noise, q=self.q, lmbda=self.lmbda,
+                          **self._qmap_args())
+
+    def _qmap_args(self):
+        """train_step's arguments of the map: the captured table stands for its size only, the values come from the
+        static rows; a device map's status is left on the device"""
+        if self.qoffsets is None:
+            return {}
+        return dict(qoffsets=self._offs, qlevels="scores" if self.qlevels is None else self.qlevels,
+                    _qmap_kw=dict(_rows=self.qoffsets, _read_status=False))
 
     def _capture(self, warmup):
         self.graph, self.out = None, None
@@ -191,12 +265,13 @@ class GraphedTrainStep:
         self.graph, self.out = g, out
         self._hyper_at_capture = self._hyper()
 
-    def __call__(self, samples, total_scores, noise=None, q=None, lmbda=None):
+    def __call__(self, samples, total_scores, noise=None, q=None, lmbda=None, qoffsets=None, qlevels=None):
         """one training step on (samples, total_scores); returns the step's device losses (static tensors,
         overwritten by the next call)"""
         if (noise is None) != (self.noise is None):
             raise ValueError("GraphedTrainStep: noise must be given at every call iff it was given at capture")
         self._refresh_q(q, lmbda)
+        self._refresh_qmap(qoffsets, qlevels)
         if self._hyper() != self._hyper_at_capture:
             self._capture(0)
         self.samples.copy_(samples, non_blocking=True)
@@ -290,13 +365,17 @@ def q_schedule(q_range, q_seed, epoch):
 
 
 def train_one_epoch(model, criterion, train_dataloader, optimizer, aux_optimizer, epoch, clip_max_norm=1.0,
-                    accum_iter=1, log=None, q_range=None, q_seed=0):
+                    accum_iter=1, log=None, q_range=None, q_seed=0, qoffsets=None):
     """utils/engine.py:30-156 (without MetricLogger / TensorBoard); returns the per-metric averages.
 
     q_range = (lo, hi): every step draws one ladder position q from a host generator seeded with
     (q_seed, epoch) and runs at the y quantiser step 2^(q/8) with the criterion's weight lmbda_for_q(criterion.lmbda,
     q).  The whole batch shares the step's q: the distortion terms are batch means, so one weight per step is what the
-    loss can honour (per-image q stays available through model.forward / train_step)."""
+    loss can honour (per-image q stays available through model.forward / train_step).
+
+    qoffsets, with or without q_range: every step runs MCM.forward_qmap with this table and levels
+    from the scores, the drawn q (0 without q_range) being the base position of the whole batch.  The criterion's
+    weight stays lmbda_for_q(criterion.lmbda, base q): which weight suits a map of steps is not measured."""
     from .rd_loss import lmbda_for_q
 
     draw = q_schedule(q_range, q_seed, epoch) if q_range is not None else None
@@ -312,7 +391,7 @@ def train_one_epoch(model, criterion, train_dataloader, optimizer, aux_optimizer
         q = next(draw) if draw is not None else None
         out = train_step(model, criterion, samples, total_scores, optimizer, aux_optimizer, clip_max_norm, accum_iter,
                          step_now=(i + 1) % accum_iter == 0, q=q,
-                         lmbda=None if q is None else lmbda_for_q(criterion.lmbda, q))
+                         lmbda=None if q is None else lmbda_for_q(criterion.lmbda, q), qoffsets=qoffsets)
         vals = torch.stack([out[k].detach().float().reshape(()) for k in METRICS]).cpu().double()
         reduced = distributed.all_reduce_mean_many(vals.tolist())
         sums += torch.tensor(reduced, dtype=torch.float64)
@@ -323,9 +402,10 @@ def train_one_epoch(model, criterion, train_dataloader, optimizer, aux_optimizer
 
 
 @torch.no_grad()
-def val_one_epoch(epoch, val_dataloader, model, criterion, q=None):
+def val_one_epoch(epoch, val_dataloader, model, criterion, q=None, qoffsets=None):
     """utils/engine.py:159-219: eval mode, no_grad, autocast (bf16 operands on MI355X).  q: the y quantiser step the
-    estimate is taken at (MCM.forward's q)"""
+    estimate is taken at (MCM.forward's q); qoffsets: the table of ladder offsets of an estimate at a
+    step per kept patch, levels from the scores (MCM.forward's qoffsets; §3.19)"""
     model.eval()
     device = next(model.parameters()).device
     sums = torch.zeros(len(METRICS), dtype=torch.float64)
@@ -334,7 +414,10 @@ def val_one_epoch(epoch, val_dataloader, model, criterion, q=None):
         samples = samples.to(device)
         total_scores = total_scores.to(device)
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            out_net = model(samples, total_scores) if q is None else model(samples, total_scores, q=q)
+            kw = {} if q is None else {"q": q}
+            if qoffsets is not None:
+                kw["qoffsets"] = qoffsets
+            out_net = model(samples, total_scores, **kw)
             out = criterion(out_net, samples)
             out["aux_loss"] = model.aux_loss()
         sums += torch.tensor([float(out[k]) for k in METRICS], dtype=torch.float64)

@@ -208,13 +208,13 @@ class MCM(CompressionModel):
         qoffsets / qlevels (eval only): compress_batch's table of ladder offsets and source of the
         per-patch levels; y is then quantised at a step per kept patch, q being the base position.  x_hat and the y
         likelihoods are bit for bit what the coder reconstructs and codes with the same arguments.  The slice loop
-        runs unchained.  Under autograd or in training mode ValueError: training with a map is not implemented."""
+        runs unchained.  Under autograd or in training mode ValueError: forward_qmap is the differentiable forward."""
         q = self._forward_q(q, imgs.shape[0])
         train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         qm = self._check_qoffsets(qoffsets, qlevels, imgs.shape[0], self._geometry()[3], "forward")
         if qm is not None and (train or self.training):
-            raise ValueError("forward: qoffsets is for evaluation (model.eval() under torch.no_grad()); training with "
-                             "a map of quantiser steps is not implemented")
+            raise ValueError("forward: qoffsets is for evaluation (model.eval() under torch.no_grad()); forward_qmap "
+                             "is the differentiable forward at a map of quantiser steps")
         if not imgs.is_cuda:
             raise ValueError("MCM.forward runs on the MI355X kernels: move the model and inputs to the GPU")
         if train:
@@ -237,7 +237,47 @@ class MCM(CompressionModel):
             return q
         return cls._check_q(q, B, "forward")
 
-    def _forward_train(self, imgs, total_scores, noise, q=None):
+    def forward_qmap(self, imgs, total_scores, noise=None, q=None, qoffsets=None, qlevels="scores", _rows=None,
+                     _read_status=True):
+        """The differentiable forward at a quantiser step per kept patch: forward(q=)'s arithmetic
+        and gradients element by element at the step of the element's own patch.  qoffsets (required) and qlevels
+        are compress_batch's: a table of 2..16 ladder offsets and the source of the per-patch levels, "scores" or an
+        integer map [B, L] in image patch order; q is the base position as forward takes it (an int, B ints or an int32
+        [B] device tensor; None: 0).  Levels and offsets are integers derived by comparisons and carry no gradient.
+
+        Under autograd or in training mode: the training node (mcm_train._MCMTrainFn) with the map; y_hat before the
+        LRP term is bit for bit what the coder reconstructs with the same arguments, and with all-zero offsets every
+        output and gradient is bitwise forward(q=)'s at a non-zero q.  Under eval() and no_grad: forward(qoffsets=)'s
+        bits, with the slice loop allowed to run chained.  A device map with an entry outside the table gives that
+        image all-zero levels and raises ValueError naming the image after the kernels have been enqueued.
+
+        _rows / _read_status are for captured calls (GraphedTrainStep, a captured eval forward): the offsets' rows as a
+        static device buffer (int32 [B, 16]), so that nothing is uploaded, and whether the status of a device map is
+        read back here."""
+        if qoffsets is None:
+            raise ValueError("forward_qmap: qoffsets (the table of ladder offsets) is required; forward(q=) is the "
+                             "path without a map")
+        B = imgs.shape[0]
+        q = self._forward_q(q, B)
+        qm = self._check_qoffsets(qoffsets, qlevels, B, self._geometry()[3], "forward_qmap")
+        if not imgs.is_cuda:
+            raise ValueError("MCM.forward_qmap runs on the MI355X kernels: move the model and inputs to the GPU")
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if train or self.training:
+            with torch.set_grad_enabled(train):
+                out = self._forward_train(imgs, total_scores, noise, q, (*qm, _rows))
+            status = self._train_exec.qm_status
+            if status is not None and _read_status:
+                _Executor._raise_levels(status.cpu().numpy(), "forward_qmap")
+            return out
+        with torch.no_grad():
+            ex = self._executor(B, imgs.device)
+            out = ex.run(imgs, total_scores, False, noise, q=q, qm=(*qm, _rows), qm_chain=True)
+            x_hat = out["x_hat"]
+            loss = self.forward_loss(imgs, x_hat) if self.distortion != "none" else (ex.zero_loss,) * 3
+        return {"loss": loss, "likelihoods": {"y": out["y"], "z": out["z"]}, "x_hat": x_hat}
+
+    def _forward_train(self, imgs, total_scores, noise, q=None, qm=None):
         """MCM.forward under autograd (utils/engine.py:75): one autograd node whose forward keeps the
         activations and whose backward is the HIP reverse pass (mcm_train.py)."""
         from .mcm_train import TrainExec, _MCMTrainFn
@@ -249,7 +289,7 @@ class MCM(CompressionModel):
         ex = getattr(self, "_train_exec", None)
         if ex is None or ex.batch != B or ex.dtype != dt or ex.device != imgs.device:
             ex = self._train_exec = TrainExec(self, B, dt, imgs.device)
-        x_hat, ylik, zlik = _MCMTrainFn.apply(ex, noise, q, imgs, total_scores, *self.parameters())
+        x_hat, ylik, zlik = _MCMTrainFn.apply(ex, noise, q, qm, imgs, total_scores, *self.parameters())
         loss = self.forward_loss(imgs, x_hat) if self.distortion != "none" else (
             torch.zeros((), device=imgs.device),) * 3
         return {"loss": loss, "likelihoods": {"y": ylik, "z": zlik}, "x_hat": x_hat}
@@ -1138,9 +1178,10 @@ class _Executor:
             raise ValueError(f"Input image size {tuple(imgs.shape[2:])} doesn't match model ({self.img})")
         return imgs
 
-    def run(self, imgs, scores, training, noise, q=None, qm=None):
+    def run(self, imgs, scores, training, noise, q=None, qm=None, qm_chain=False):
         """q: None, B ladder positions (uploaded once, before the first launch) or an int32 [B] device tensor; qm:
-        MCM._check_qoffsets' pair (eval only): the slice loop then runs unchained at a step per kept patch"""
+        MCM._check_qoffsets' pair (eval only): the slice loop then runs at a step per kept patch, unchained as the
+        coders run it, or with qm_chain (forward_qmap) chained with the map in the launches' cqm"""
         m, B = self.m, self.batch
         qd = self._q_dev(q)
         if qm is not None:
@@ -1173,7 +1214,7 @@ class _Executor:
             self._slices(self._gc_forward(y_noise, qd), chain_ok=True, cq=qd)
         else:
             qmap, lstatus = self._encode_map(qm, scores, shuf, qd)
-            self._slices(self._gc_forward(y_noise, None, qmap))
+            self._slices(self._gc_forward(y_noise, None, qmap), chain_ok=qm_chain, cqm=qmap)
 
         x_hat = self._back(shuf, imgs.shape[1])
         if qm is not None and lstatus is not None:
@@ -1230,8 +1271,10 @@ class _Executor:
         -> (offsets tuple, "scores" | int32 device tensor, device offsets [B, 16], whether the device checks the map)"""
         from .bitstream import offsets_row
 
-        offs, src = qm
-        rows = torch.tensor([offsets_row(offs)] * self.batch, dtype=torch.int32).to(self.device)
+        offs, src = qm[0], qm[1]
+        rows = qm[2] if len(qm) > 2 else None  # forward_qmap's _rows: already on the device (a captured forward)
+        if rows is None:
+            rows = torch.tensor([offsets_row(offs)] * self.batch, dtype=torch.int32).to(self.device)
         on_device = torch.is_tensor(src)
         if isinstance(src, np.ndarray):
             src = torch.from_numpy(src).to(self.device)
@@ -1653,7 +1696,7 @@ class _Executor:
                 cin = cout
             x, xs = out, out[0].numel()
 
-    def _slices(self, gc_step, chain_ok=False, cq=None):
+    def _slices(self, gc_step, chain_ok=False, cq=None, cqm=None):
         m, dt, B, g = self.m, self.dtype, self.batch, self.g
         M, S, sw, ms, nb, Mp = m.latent_depth, m.num_slices, self.sw, self.maxsup, self.nb, self.Mp
         mid = self.mid
@@ -1806,7 +1849,7 @@ class _Executor:
             lb_ = [self.lrp_first[i][1]] + [b for _, b in self.lrp_layers[i]]
             ch = dict(w=lw, b=lb_, couts=mid, x1=supy, c1=sw * i, ld1=M, y=yv + i * sw * e4, ldy=M,
                       add=pbase + (off_lrp + i * c0) * eP, ld_add=Pw, ypre=ypre + i * sw * e4, ld_ypre=M,
-                      out=yh + i * sw * esz, ld_out=M, out2=supy + i * sw * esz, ld_out2=M, q=cq)
+                      out=yh + i * sw * esz, ld_out=M, out2=supy + i * sw * esz, ld_out2=M, q=cq, qm=cqm)
             ops.lic_stack(B, g, supy, sw * i, M, ws, bs_, mid, ms_ser + i * Mp * sw * e4, sw, True,
                           addend=pbase + (off_mean + i * c0) * eP, ld_add=Pw, nb=(2, 1), strides=st, chain=ch)
 

@@ -21,6 +21,7 @@ the MAE executor vit_train._VitTrainBase.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -117,11 +118,17 @@ class TrainExec(_VitTrainBase):
         return uniq
 
     # ------------------------------------------------------------------ forward
-    def forward(self, imgs, scores, noise, q=None):
-        """q: None, B ladder positions (uploaded once, before the first launch) or an int32 [B] device tensor"""
+    def forward(self, imgs, scores, noise, q=None, qm=None):
+        """q: None, B ladder positions (uploaded once, before the first launch) or an int32 [B] device tensor.
+        qm: None, or MCM._check_qoffsets' pair (the table of offsets, "scores" or a map of levels in
+        image patch order), optionally followed by the offsets' rows already on the device (int32 [B, 16], a captured
+        step's static buffer).  q is then the base position; the levels are selected once, after ids_shuffle exists,
+        and the map of clamped ladder positions (self.qmd, int32 [B, K]) stays for the backward."""
         m, B, g = self.m, self.batch, self.g
         M, N, hz = m.latent_depth, m.hyperprior_depth, self.hz
         self.qd = q if q is None or torch.is_tensor(q) else torch.tensor(q, dtype=torch.int32).to(self.device)
+        self.qmd = self.qm_status = None
+        self._qm = None if qm is None else self._map_upload(qm)
         imgs = self._begin(imgs)
         if noise is not None:
             self.z_noise, self.y_noise = (t.float().contiguous() for t in noise)
@@ -131,9 +138,40 @@ class TrainExec(_VitTrainBase):
             self.z_noise = torch.empty((B, N, hz, hz), device=self.device).uniform_(-0.5, 0.5)
             self.y_noise = torch.empty((B, M, g, g), device=self.device).uniform_(-0.5, 0.5)
         self.enc_out = self.enc_fwd(imgs, scores)
+        if self._qm is not None:
+            self._build_map(scores)
         self._lic_fwd(self.enc_out)
         x_hat = self.dec_fwd(self.gs_out)
         return x_hat, self.YLIK, self.ZLIK
+
+    # ------------------------------------------------------------------ per-patch quantiser steps
+    def _map_upload(self, qm):
+        """the eval executor's _map_upload: everything of qm that lives on the host goes up before the first launch ->
+        (table size, "scores" | int32 [B, L] device tensor, device offsets [B, 16], whether the device checks the map)"""
+        from .bitstream import offsets_row
+
+        offs, src = qm[0], qm[1]
+        rows = qm[2] if len(qm) > 2 and qm[2] is not None else None
+        if rows is None:
+            rows = torch.tensor([offsets_row(offs)] * self.batch, dtype=torch.int32).to(self.device)
+        on_device = torch.is_tensor(src)
+        if isinstance(src, np.ndarray):
+            src = torch.from_numpy(src).to(self.device)
+        return len(offs), src, rows, on_device
+
+    def _build_map(self, scores):
+        """levels of the kept patches (tmae_qlevels_select: from the scores, or the caller's map gathered by
+        ids_shuffle), then the clamped ladder positions at the base q (tmae_qmap_build) -> self.qmd; the levels carry
+        no gradient.  self.qm_status: int32 [B] on the device when the map came from the device (1 = an entry outside
+        the table, that image's levels all zero), else None.  Nothing is read back."""
+        nlev, src, rows, on_device = self._qm
+        K = self.m.num_keep_patches
+        if isinstance(src, str):
+            self.qm_levels, _ = ops.qlevels_select(self.shuf, K, nlev, scores=scores.float().contiguous())
+        else:
+            self.qm_levels, status = ops.qlevels_select(self.shuf, K, nlev, level_map=src)
+            self.qm_status = status if on_device else None
+        self.qmd = ops.qmap_build(self.qm_levels, self.qd, rows)
 
     def _begin(self, imgs):
         """what every forward entry starts with: the image check and the weight copies' refresh"""
@@ -385,7 +423,8 @@ class TrainExec(_VitTrainBase):
             ch = dict(w=[w[0] for w in lw], b=[b[0] for b in lb], couts=mid, x1=lms + M * esz, c1=ny, ld1=2 * M,
                       y=self.Y32.data_ptr() + i * sw * e4, ldy=M, add=pb + (off_lrp + i * c0) * e4, ld_add=Pw,
                       ypre=self.YPRE.data_ptr() + i * sw * e4, ld_ypre=M, out=self.YH.data_ptr() + i * sw * esz,
-                      ld_out=M, out2=lms + (M + i * sw) * esz, ld_out2=2 * M, q=self.qd)
+                      ld_out=M, out2=lms + (M + i * sw) * esz, ld_out2=2 * M,
+                      q=self.qd if self.qmd is None else None, qm=self.qmd)
             save = {"layers": [(pre, act, (Mp * c, 0)) for (act, pre), c in zip(sv_ms, mid)],
                     "chain": [(pre, act, 0) for act, pre in sv_l], "chain_t": t}
             ops.lic_stack(B, g, lms + M * esz, ny, 2 * M, [w[0] for w in ws], [b[0] for b in bs], mid, MS[0, i], sw,
@@ -434,14 +473,18 @@ class TrainExec(_VitTrainBase):
         M, sw, Mp, HW = self.m.latent_depth, self.sw, self.Mp, self.g * self.g
         args = (self.Y32, M, i0 * sw, mu, sigma, Mp * sw, sw, self.y_noise, self.YLIK, M, self.YPT, self.dtype, M,
                 self.YPRE, M, self.batch, HW, nbs, sw)
-        if self.qd is None:
+        if self.qmd is not None:
+            ops.gc_slices_fwd_qm(*args, self.scale_bound, self.qmd)
+        elif self.qd is None:
             ops.gc_slices(*args)
         else:
             ops.gc_slices_fwd_q(*args, self.scale_bound, self.qd)
 
     def _gc_bwd(self, *args):
-        """T.gc_bwd, at the forward's quantiser step when it had one"""
-        if self.qd is None:
+        """T.gc_bwd, at the forward's quantiser step, or its map of steps, when it had one"""
+        if self.qmd is not None:
+            T.gc_bwd_qm(*args, self.scale_bound, self.qmd)
+        elif self.qd is None:
             T.gc_bwd(*args)
         else:
             T.gc_bwd_q(*args, self.scale_bound, self.qd)
@@ -985,8 +1028,8 @@ class _MCMTrainFn(torch.autograd.Function):
     """MCM.forward as one autograd node: (imgs, scores, *params) -> (x_hat, y likelihood, z likelihood)"""
 
     @staticmethod
-    def forward(ctx, ex, noise, q, imgs, scores, *params):
-        x_hat, ylik, zlik = ex.forward(imgs, scores, noise, q)
+    def forward(ctx, ex, noise, q, qm, imgs, scores, *params):
+        x_hat, ylik, zlik = ex.forward(imgs, scores, noise, q, qm)
         ctx.ex = ex
         ctx.params = params
         return x_hat, ylik, zlik
@@ -1010,7 +1053,7 @@ class _MCMTrainFn(torch.autograd.Function):
             else:
                 off = ex.offsets[id(p)]
                 out.append(gflat[off:off + p.numel()].view(p.shape))
-        return (None, None, None, None, None, *out)
+        return (None, None, None, None, None, None, *out)
 
 
 # ---------------------------------------------------------------------- forward_encoder / forward_decoder alone

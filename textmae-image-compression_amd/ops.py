@@ -412,6 +412,8 @@ def lic_stack(n, G, x1, c1, ld1, weights, biases, couts, y, ldy, y_f32, x2=None,
         a.cy, a.cldy = _p(chain["out"]), chain["ld_out"]
         a.cy2, a.cldy2 = _p(chain.get("out2")), chain.get("ld_out2", 0)
         a.cq = _q_ptr(chain.get("q"), n)  # per-image quantiser step of y_hat_pre or None
+        if chain.get("qm") is not None:  # a step per pixel of the grid: int32 [n, G * G]
+            a.cqm = _qmap_ptr(chain["qm"], n, G * G)
         cs = chain.get("strides", {})  # per-slice (b2) element strides of the chain operands
         a.cs_x1, a.cs_yv, a.cs_src = cs.get("x1", 0), cs.get("y", 0), cs.get("ypre", 0)
         a.cs_add, a.cs_y, a.cs_y2 = cs.get("add", 0), cs.get("out", 0), cs.get("out2", 0)

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDgradArgs, WgradArgs
-from .ops import _p, _q_ptr, _stream, dtype_code
+from .ops import _p, _q_ptr, _qmap_ptr, _stream, dtype_code
 
 _SCRATCH: dict = {}
 
@@ -218,6 +218,15 @@ def gc_bwd_q(y, ldy, yoff, mu, sigma, ld_ms, noise, Mtot, glik, gyp, ldg, dy, ld
     _lib.call("tmae_gc_bwd_q", _p(y), ldy, yoff, _p(mu), _p(sigma), ld_ms, _p(noise), Mtot, _p(glik), _p(gyp), ldg,
               _p(dy), lddy, _p(dmu), _p(dsigma), ldd, n, HW, sw, dtype_code(dtype), float(scale_bound),
               _q_ptr(q, n), _stream())
+
+
+def gc_bwd_qm(y, ldy, yoff, mu, sigma, ld_ms, noise, Mtot, glik, gyp, ldg, dy, lddy, dmu, dsigma, ldd, n, HW, sw, dtype,
+              scale_bound, qmap):
+    """gc_bwd_q at a quantiser step per pixel of the latent grid: the backward of
+    ops.gc_slices_fwd_qm; qmap int32 [n, HW] on the device (ops.qmap_build), required"""
+    _lib.call("tmae_gc_bwd_qm", _p(y), ldy, yoff, _p(mu), _p(sigma), ld_ms, _p(noise), Mtot, _p(glik), _p(gyp), ldg,
+              _p(dy), lddy, _p(dmu), _p(dsigma), ldd, n, HW, sw, dtype_code(dtype), float(scale_bound),
+              _qmap_ptr(qmap, n, HW), _stream())
 
 
 def gc_bwd(y, ldy, yoff, mu, sigma, ld_ms, noise, Mtot, glik, gyp, ldg, dy, lddy, dmu, dsigma, ldd, n, HW, sw, dtype):

@@ -377,6 +377,23 @@ int tmae_gc_slices_fwd_qm(const float* y, int ldy, int yoff, const float* mu, co
                           float* yhat32, int ld32, int n, int HW, int nslices, int sw, float scale_bound,
                           const int* qmap, void* stream);
 
+/* tmae_gc_slices_code_q / _qm with rate-distortion optimised quantisation (csrc/gc_rdo.h): per element
+ * the rounded symbol qi0 or, when w[image] (bits(r, qi0) - bits(r, qi1)) > delta^2 (e1^2 - e0^2) strictly, the one
+ * candidate qi1 one step toward zero; w = 0 is plain rounding bit for bit.  Arguments and layouts up to scale_bound are
+ * tmae_gc_slices_code_q's.  q: device int32 [n] or NULL; qmap: device int32 [n][HW] or NULL, takes precedence; both
+ * NULL: step 1.  rdo_w: device float [n], required, >= 0 and finite (squared latent units per bit).  rate: device float
+ * [nscale][rate_stride], rate[r][k] = 16 - log2(cdf[r][k + 1] - cdf[r][k]) as the host builds it from the tables the
+ * coder uses (GaussianConditional.rate_table); cdf_sizes / cdf_offsets: device int32 [nscale], those tables' row sizes
+ * and offsets.  A symbol outside its row costs the escape symbol plus 4 (1 + digits) bits, as the coder codes it.
+ * changed: device int32 [n] or NULL, the caller zeroes it: the elements of image b whose symbol is not qi0 are added.
+ * Both launch forms, bitwise equal.  The decoder takes no part: tmae_gc_dequantize_q / _qm decode the result. */
+int tmae_gc_slices_code_rdo(const float* y, int ldy, int yoff, const float* mu, const float* sigma,
+                            long long ms_stride, int ld_ms, float* lik, int Mtot, void* yhat, int yhat_dtype,
+                            int ld_yhat, float* yhat32, int ld32, int n, int HW, int nslices, int sw, int* symbols,
+                            int* indexes, const float* scale_table, int nscale, float scale_bound, const int* q,
+                            const int* qmap, const float* rdo_w, const float* rate, int rate_stride,
+                            const int* cdf_sizes, const int* cdf_offsets, int* changed, void* stream);
+
 /* GaussianConditional.update (update_scale_table): pmf[n][max_length], tail[n] for the CDF builder */
 int tmae_gc_pmf(const float* scale_table, const int* pmf_center, int n, int max_length, float* pmf, float* tail,
                 void* stream);

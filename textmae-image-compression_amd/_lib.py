@@ -163,6 +163,9 @@ SIGNATURES = {
     "tmae_gc_indexes_qm": [P, LL, I, I, I, I, I, P, I, F, P, P, P],
     "tmae_gc_dequantize_qm": [P, P, LL, I, I, I, I, I, I, P, I, I, P, I, P, P],
     "tmae_gc_slices_fwd_qm": [P, I, I, P, P, LL, I, P, P, I, P, I, I, P, I, I, I, I, I, F, P, P],
+    # the encoder's slice kernel with rate-distortion optimised quantisation (csrc/coding_rdo.hip)
+    "tmae_gc_slices_code_rdo": [P, I, I, P, P, LL, I, P, I, P, I, I, P, I, I, I, I, I, P, P, P, I, F, P, P, P, P, I, P,
+                                P, P, P],
     "tmae_gc_pmf": [P, P, I, I, P, P, P],
     "tmae_eb_pmf": [ctypes.POINTER(EBParams), P, P, I, I, P, P, P],
     "tmae_eb_symbols": [P, ctypes.POINTER(EBParams), P, I, I, I, P, P],

@@ -6,6 +6,7 @@
     python -m textmae_amd.codec decode --region X,Y,W,H -c CKPT -d OUT -o PNGS
     python -m textmae_amd.codec encode [--tiled] --q N | --target-bytes N ...
     python -m textmae_amd.codec encode [--tiled] --q-offsets A,B,C,... [--q N | --target-bytes N] ...
+    python -m textmae_amd.codec encode [--tiled] --rdoq W [--q N | --target-bytes N] [--q-offsets A,B,C,...] ...
 
 ``encode --tiled`` codes every image at its own resolution as overlapping model-sized tiles (MCM.encode_image,
 one ``<name>.tmt`` each); ``decode`` takes ``.tmt`` files next to ``.tmc`` ones and saves them at their native size.
@@ -21,6 +22,11 @@ the kept patches of an image (of a tile with ``--tiled``) are ranked by their te
 as there are offsets, the most text-like share first, and level l is coded at ladder position N + offset l (clamped
 to -32..32), N being ``--q`` (default 0) or what ``--target-bytes`` picks.  The files record the table and the
 levels; ``decode`` needs no flag.
+
+``encode --rdoq W`` lets the encoder move a y symbol one step toward zero where W times the bits that
+saves through the symbol's own CDF row exceeds the squared latent error it adds; W >= 0, in squared latent units per
+bit, 0 being plain rounding.  It works with ``--q``, ``--target-bytes``, ``--q-offsets`` and ``--tiled``; the files
+are of the same kinds, record nothing of it, and ``decode`` needs no flag.
 
 ``encode`` reads FOLDER through ``data.ImageFolderLoader`` (the test transform: bicubic resize to the model's
 size, scores from ``<FOLDER>_scores/test.pt`` or the device producer) and writes one ``<name>.tmc`` per image,
@@ -71,7 +77,7 @@ def encode_tiled(args, model):
     for p in files:
         a = np.array(Image.open(p).convert("RGB"))
         blob = model.encode_image(a, overlap=args.overlap, lanes=args.lanes, tile_batch=args.batch, q=args.q,
-                                  target_bytes=args.target_bytes, qoffsets=args.q_offsets)
+                                  target_bytes=args.target_bytes, qoffsets=args.q_offsets, rdoq=args.rdoq)
         _warn_target(args, p.name, blob)
         with open(os.path.join(args.output, p.stem + ".tmt"), "wb") as f:
             f.write(blob)
@@ -93,7 +99,7 @@ def encode(args):
     paths, done, nbytes = loader.imgs_path, 0, 0
     for imgs, ori_shapes, scores in loader:  # unshuffled: batch i holds paths[done : done + B]
         blobs = model.encode_bytes(imgs, scores, lanes=args.lanes, orig_sizes=ori_shapes, q=args.q,
-                                   target_bytes=args.target_bytes, qoffsets=args.q_offsets)
+                                   target_bytes=args.target_bytes, qoffsets=args.q_offsets, rdoq=args.rdoq)
         for p, blob in zip(paths[done:done + len(blobs)], blobs):
             _warn_target(args, p.name, blob)
             with open(os.path.join(args.output, p.stem + ".tmc"), "wb") as f:
@@ -195,12 +201,29 @@ def setup_args():
     q.add_argument("--q-offsets", type=q_offsets, default=None, metavar="A,B,C,...", dest="q_offsets",
                    help="a quantiser step per kept patch: 2..16 ladder offsets, the first for the most text-like "
                         "share of the kept patches (added to --q or to what --target-bytes picks)")
+    q.add_argument("--rdoq", type=_rdoq, default=None, metavar="W",
+                   help="rate-distortion optimised quantisation of y: a symbol moves one step toward zero where W "
+                        "times the bits that saves exceeds the squared latent error it adds (W >= 0, 0 = plain "
+                        "rounding); with --q, --target-bytes, --q-offsets and --tiled; decode needs no flag")
     sub.choices["decode"].add_argument("--original_size", action="store_true",
                                        help="save each output resized to the size its file recorded")
     sub.choices["decode"].add_argument("--region", type=_region, default=None, metavar="X,Y,W,H",
                                        help="of every .tmt file, decode and save only this window (origin X,Y, "
                                             "size W x H), from the tiles it needs")
     return p
+
+
+def _rdoq(text):
+    """--rdoq W -> the weight as a float (MCM._check_rdoq's conditions)"""
+    import math
+
+    try:
+        w = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--rdoq {text!r} is not a number") from None
+    if not (math.isfinite(w) and w >= 0):
+        raise argparse.ArgumentTypeError(f"--rdoq {text} must be finite and >= 0")
+    return w
 
 
 def main(argv):

@@ -24,7 +24,8 @@ import torch
 from . import _lib
 
 __all__ = ["BufferedRansEncoder", "RansEncoder", "RansDecoder", "pmf_to_quantized_cdf", "DeviceRansEncoder",
-           "DeviceRansDecoder", "lane_split", "encode_record", "decode_record", "parse_record"]
+           "DeviceRansDecoder", "lane_split", "encode_record", "decode_record", "parse_record", "rate_table",
+           "symbol_bits", "table_bits"]
 
 
 def _i32(x) -> np.ndarray:
@@ -136,6 +137,51 @@ class RansDecoder:
             return self.decode_stream(indexes, cdfs, cdf_sizes, offsets)
         finally:
             self._close()
+
+
+# ------------------------------------------------------------------ what a symbol costs
+def rate_table(cdf, cdf_sizes, precision: int = 16) -> np.ndarray:
+    """float32 [n][len - 1]: B[r][k] = float32(precision - log2(float64(cdf[r][k + 1] - cdf[r][k]))) for
+    k < cdf_sizes[r] - 1 (the last of them is the row's escape symbol), 0 past the row"""
+    cdf, sizes = np.asarray(cdf, dtype=np.int64), np.asarray(cdf_sizes, dtype=np.int64).reshape(-1)
+    if cdf.ndim != 2 or sizes.size != cdf.shape[0] or (sizes < 2).any() or (sizes > cdf.shape[1]).any():
+        raise ValueError(f"rate_table: cdf {cdf.shape} with {sizes.size} sizes: one size in 2..{cdf.shape[-1]} per row")
+    freq = np.diff(cdf, axis=1)
+    inside = np.arange(freq.shape[1])[None, :] < (sizes - 1)[:, None]
+    if (freq[inside] <= 0).any():
+        raise ValueError("rate_table: a CDF row is not strictly increasing inside its length")
+    bits = float(precision) - np.log2(np.where(inside, freq, 1).astype(np.float64))
+    return np.ascontiguousarray(np.where(inside, bits, 0.0).astype(np.float32))
+
+
+def symbol_bits(symbols, indexes, rate, cdf_sizes, offsets) -> np.ndarray:
+    """float32 per symbol: what the coder spends on symbols[i] through row indexes[i] of `rate` (rate_table), by the
+    coder's clamp and escape rule: value = symbol - offset; inside [0, size - 2) it is rate[row][value], otherwise the
+    escape symbol rate[row][size - 2] plus 4 (1 + ndig) bits, ndig the 4-bit digits of raw = -2 value - 1 below the
+    support and 2 (value - (size - 2)) above it"""
+    sym, idx = np.asarray(symbols, dtype=np.int64).reshape(-1), np.asarray(indexes, dtype=np.int64).reshape(-1)
+    if sym.size != idx.size:
+        raise ValueError(f"{sym.size} symbols but {idx.size} indexes")
+    rate = np.asarray(rate, dtype=np.float32)
+    if idx.size and (idx.min() < 0 or idx.max() >= rate.shape[0]):
+        raise ValueError("symbol_bits: a CDF index outside the tables")
+    maxv = np.asarray(cdf_sizes, dtype=np.int64).reshape(-1)[idx] - 2
+    value = sym - np.asarray(offsets, dtype=np.int64).reshape(-1)[idx]
+    esc = (value < 0) | (value >= maxv)
+    raw = np.where(value < 0, -2 * value - 1, 2 * (value - maxv))
+    raw = np.where(esc, raw, 0)
+    ndig = np.zeros(sym.size, dtype=np.int64)
+    for d in range(1, 9):
+        ndig[raw >= (1 << (4 * (d - 1)))] = d
+    base = rate[idx, np.where(esc, maxv, value)]
+    return np.where(esc, base + (4 * (1 + ndig)).astype(np.float32), base).astype(np.float32)
+
+
+def table_bits(symbols, indexes, cdf, cdf_sizes, offsets) -> float:
+    """the bits the coder spends on the symbols under the tables' own frequencies (the float64 sum of symbol_bits):
+    the length of their record up to the coder's flush and its 0.1 %"""
+    t, sizes, offs = _tables(cdf, cdf_sizes, offsets)
+    return float(symbol_bits(symbols, indexes, rate_table(t, sizes), sizes, offs).astype(np.float64).sum())
 
 
 # ------------------------------------------------------------------ lane-interleaved records (host side)

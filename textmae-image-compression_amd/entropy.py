@@ -97,6 +97,30 @@ class EntropyModel(nn.Module):
             self._device_tables_cache = cache
         return cache[2]
 
+    def rate_table(self):
+        """what the coder spends per symbol of every CDF row, in bits: float32 [n][len - 1] numpy,
+        B[r][k] = float32(16 - log2(float64(cdf[r][k + 1] - cdf[r][k]))) for k < cdf_length[r] - 1 (k =
+        cdf_length[r] - 2 is the row's escape symbol) and 0 past the row; built on the host from host_tables() and
+        cached with them.  16 is the coder's precision (entropy_coder_precision)."""
+        tabs = self.host_tables()
+        cache = getattr(self, "_rate_table_cache", None)
+        if cache is None or cache[0] is not tabs:
+            from .coder import rate_table
+
+            cache = (tabs, rate_table(tabs[0], tabs[1], self.entropy_coder_precision))
+            self._rate_table_cache = cache
+        return cache[1]
+
+    def device_rate_table(self, device=None):
+        """rate_table() as a float32 device tensor, cached like device_tables()"""
+        tab = self.rate_table()
+        device = torch.device(device) if device is not None else self._quantized_cdf.device
+        cache = getattr(self, "_device_rate_table_cache", None)
+        if cache is None or cache[0] is not tab or cache[1] != device:
+            cache = (tab, device, torch.from_numpy(tab).to(device))
+            self._device_rate_table_cache = cache
+        return cache[2]
+
     @staticmethod
     def quantize_symbols(inputs, means=None):
         """quantize(inputs, "symbols", means): round(inputs - means).int() (module-level convenience)"""

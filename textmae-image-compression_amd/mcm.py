@@ -18,9 +18,11 @@ operand type: torch.float32 (exact f32 MFMA; the parity path, default) or torch.
 from __future__ import annotations
 
 import collections.abc
+import math
 import os
 
 from functools import partial
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -440,6 +442,29 @@ class MCM(CompressionModel):
         return qs if any(qs) else None
 
     @staticmethod
+    def _check_rdoq(rdoq, B, who):
+        """rdoq= of the encode methods -> None (plain rounding with today's kernels) or a list of B weights >= 0, in
+        squared latent units per bit; a float stands for all B images.  ValueError before anything
+        is launched"""
+        if rdoq is None:
+            return None
+        if np.ndim(rdoq) == 0:
+            ws = [rdoq] * B
+        else:
+            ws = list(rdoq.tolist() if hasattr(rdoq, "tolist") else rdoq)
+            if len(ws) != B:
+                raise ValueError(f"{who}: {len(ws)} entries of rdoq for {B} images: one per image, or one float for all")
+        out = []
+        for b, v in enumerate(ws):
+            if isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{who}: rdoq[{b}] = {v!r} is not a number")
+            v = float(v)
+            if not (math.isfinite(v) and v >= 0.0) or v > float(np.finfo(np.float32).max):
+                raise ValueError(f"{who}: rdoq[{b}] = {v!r} must be finite and >= 0")
+            out.append(v)
+        return out
+
+    @staticmethod
     def _check_qoffsets(qoffsets, qlevels, B, L, who, K=None):
         """qoffsets= / qlevels= of the batch methods -> None (no map) or (the offsets as a tuple, the source of the
         levels): "scores", an int32 numpy array checked here, or the caller's device tensor (checked on the device).
@@ -472,7 +497,8 @@ class MCM(CompressionModel):
             raise ValueError(f"{who}: qlevels of image {int(bad[0])}: a level outside 0..{len(offs) - 1}")
         return offs, np.ascontiguousarray(a, dtype=np.int32)
 
-    def compress_batch(self, imgs, total_scores, lanes=1, z_lanes=None, q=None, qoffsets=None, qlevels=None):
+    def compress_batch(self, imgs, total_scores, lanes=1, z_lanes=None, q=None, qoffsets=None, qlevels=None,
+                       rdoq=None):
         """compress with one independent record per image, coded on the device (csrc/rans_device.hip) ->
         {"string": [y_strings, z_strings], "shape", "ids_restore"}, len(y_strings) == len(z_strings) == B.
         Image b's (y_strings[b], z_strings[b]) are the strings MCM.compress (MCM.py:805-894) returns for that image
@@ -494,11 +520,19 @@ class MCM(CompressionModel):
         the most text-like share) or an integer map [B, L] in image patch order (the layout of total_scores), a numpy
         array or an int32 device tensor; an entry outside the table raises ValueError naming the image.  The result
         then carries "qoffsets" and "qlevels" (int32 [B, K] on the device, kept order), which decompress_batch needs
-        together with q."""
+        together with q.
+
+        rdoq: rate-distortion optimised quantisation of y, a weight >= 0 in squared latent units per
+        bit, a float or B floats.  Every non-zero y symbol may then move one step toward zero where the bits that
+        saves through its own CDF row, times the weight, exceed the latent error it adds (csrc/gc_rdo.h).  None is
+        the path above with its kernels and bytes; 0.0 takes the new kernel and gives the same bytes.  It works with
+        q and with qoffsets; the decoder needs nothing, decompress_batch takes the same arguments as without it.  The
+        result then carries "rdoq" and last_streams["y_changed"] the moved symbols per image.  z is not touched."""
         from .coder import check_lanes
 
         lanes, z_lanes = check_lanes(lanes), check_lanes(1 if z_lanes is None else z_lanes)
         q = self._check_q(q, imgs.shape[0], "compress_batch")
+        rdoq = self._check_rdoq(rdoq, imgs.shape[0], "compress_batch")
         qm = self._check_qoffsets(qoffsets, qlevels, imgs.shape[0], self._geometry()[3], "compress_batch")
         if not imgs.is_cuda:
             raise ValueError("MCM.compress_batch runs on the MI355X kernels: move the model and inputs to the GPU")
@@ -506,7 +540,7 @@ class MCM(CompressionModel):
         self.gaussian_conditional._check_cdf()
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            return ex.compress_batch(imgs, total_scores, lanes, z_lanes, q, qm=qm)
+            return ex.compress_batch(imgs, total_scores, lanes, z_lanes, q, qm=qm, rdoq=rdoq)
 
     def decompress_batch(self, strings, shape, ids_restore=None, lanes=1, z_lanes=None, q=None, qoffsets=None,
                          qlevels=None):
@@ -545,7 +579,7 @@ class MCM(CompressionModel):
         return int(pe.img_size[0]), int(pe.patch_size[0]), int(self.num_keep_patches), int(pe.num_patches)
 
     def encode_bytes(self, imgs, total_scores, lanes=1, z_lanes=None, orig_sizes=None, q=None, target_bytes=None,
-                     qoffsets=None, qlevels=None):
+                     qoffsets=None, qlevels=None, rdoq=None):
         """compress_batch into self-contained bitstreams -> list of B bytes objects (bitstream.py, container version
         1): header (geometry, lanes, original size), the kept patch ids packed on the device (ops.ids_pack, at
         ceil(log2 L) bits each), then compress_batch's z and y records of the image as they are.  decode_bytes needs
@@ -562,10 +596,15 @@ class MCM(CompressionModel):
         qoffsets / qlevels: compress_batch's; every image then becomes a TPC blob that records its
         base q (0 included), the table and the levels of its kept patches, packed on the device (ops.qlevels_pack).
         With target_bytes the bisection runs over the base q as above, the map being rebuilt per probe, and the size
-        counts the TPC header and the level words."""
+        counts the TPC header and the level words.
+
+        rdoq: compress_batch's, a float or B floats.  The blobs are of the same kinds and decode
+        with decode_bytes as they are: nothing of it is recorded.  With target_bytes the weight is the same in every
+        probe and the bisection is unchanged."""
         from . import bitstream
 
         B = imgs.shape[0]
+        rdoq = self._check_rdoq(rdoq, B, "encode_bytes")
         if orig_sizes is not None and len(orig_sizes) != B:
             raise ValueError(f"{len(orig_sizes)} original sizes for {B} images")
         if q is not None and target_bytes is not None:
@@ -579,10 +618,11 @@ class MCM(CompressionModel):
             else:
                 size = lambda v: bitstream.PHEADER_BYTES + fixed + 4 * bitstream.level_words(K, len(qm[0]))  # noqa: E731
             lanes, z_lanes, ids, z, y, qs, lev = self._encode_sections_target(
-                imgs, total_scores, lanes, z_lanes, self._check_targets(target_bytes, B, "encode_bytes"), size, qm)
+                imgs, total_scores, lanes, z_lanes, self._check_targets(target_bytes, B, "encode_bytes"), size, qm,
+                rdoq)
         else:
             qs = self._check_q(q, B, "encode_bytes") or [0] * B
-            lanes, z_lanes, ids, z, y, lev = self._encode_sections(imgs, total_scores, lanes, z_lanes, qs, qm)
+            lanes, z_lanes, ids, z, y, lev = self._encode_sections(imgs, total_scores, lanes, z_lanes, qs, qm, rdoq)
         return [bitstream.assemble(img, K, patch, lanes, z_lanes, None if orig_sizes is None else orig_sizes[b],
                                    ids[b], z[b], y[b], qs[b], *(() if qm is None else (qm[0], lev[b])))
                 for b in range(B)]
@@ -607,17 +647,18 @@ class MCM(CompressionModel):
         both = torch.cat([ids, ops.qlevels_pack(self._exec.last_levels, len(qm[0]))], dim=1).cpu().numpy()
         return both[:, :W], both[:, W:]
 
-    def _encode_sections(self, imgs, total_scores, lanes, z_lanes, q=None, qm=None):
+    def _encode_sections(self, imgs, total_scores, lanes, z_lanes, q=None, qm=None, rdoq=None):
         """the sections of encode_bytes' blobs (and of encode_image's tiles) -> (lanes, z_lanes, id words uint32-
         compatible numpy [B, W], z records, y records, level words [B, W2] or None): compress_batch, then the kept ids
         (and with a map qm = _check_qoffsets' pair the levels) packed on the device"""
-        out = self.compress_batch(imgs, total_scores, lanes, z_lanes, q, *((None, None) if qm is None else qm))
+        out = self.compress_batch(imgs, total_scores, lanes, z_lanes, q, *((None, None) if qm is None else qm),
+                                  rdoq=rdoq)
         lanes, z_lanes = out.get("lanes", (1, 1))
         ids, lev = self._side_words(qm)
         y, z = out["string"]
         return lanes, z_lanes, ids, z, y, lev
 
-    def _encode_sections_target(self, imgs, total_scores, lanes, z_lanes, targets, fixed_bytes, qm=None):
+    def _encode_sections_target(self, imgs, total_scores, lanes, z_lanes, targets, fixed_bytes, qm=None, rdoq=None):
         """_encode_sections with per image the smallest q whose blob fits targets[b] -> (..., y records, q per image,
         level words); fixed_bytes(q): the bytes of a blob at q besides its z and y records"""
         from .coder import check_lanes
@@ -629,7 +670,8 @@ class MCM(CompressionModel):
         self.gaussian_conditional._check_cdf()
         with torch.no_grad():
             ex = self._executor(imgs.shape[0], imgs.device)
-            z, y, qs = ex.compress_batch_target(imgs, total_scores, lanes, z_lanes, targets, fixed_bytes, qm=qm)
+            z, y, qs = ex.compress_batch_target(imgs, total_scores, lanes, z_lanes, targets, fixed_bytes, qm=qm,
+                                                rdoq=rdoq)
         ids, lev = self._side_words(qm)
         return lanes, z_lanes, ids, z, y, qs, lev
 
@@ -714,7 +756,7 @@ class MCM(CompressionModel):
         return {"x_hat": x_hat, "orig_sizes": [p.orig_size for p in parsed]}
 
     def encode_image(self, rgb_u8, overlap=32, lanes=1, z_lanes=None, tile_batch=16, q=None, target_bytes=None,
-                     qoffsets=None):
+                     qoffsets=None, rdoq=None):
         """an image at its own resolution -> one TMT file (bitstream.assemble_image).  rgb_u8: uint8
         [H, W, 3], numpy or tensor (a host image is uploaded once).  The image is cut into overlapping model-sized
         tiles (tiling.py; overlap 0..img_size // 2) and every chunk of tile_batch tiles (the last may be smaller)
@@ -730,7 +772,10 @@ class MCM(CompressionModel):
 
         qoffsets: compress_batch's table of ladder offsets; every tile's kept patches get their
         levels from the tile's own scores and the file becomes a TPT file with that one table, q (or the q that
-        target_bytes picks) its base position."""
+        target_bytes picks) its base position.
+
+        rdoq: compress_batch's weight as one float for every tile of the file, the same in every
+        probe of target_bytes; the file is of the same kind and decode_image / decode_region read it as they are."""
         from . import bitstream, tiling
         from .coder import check_lanes
         from .scores import image_scores
@@ -752,6 +797,9 @@ class MCM(CompressionModel):
             raise ValueError("encode_image: give q or target_bytes, not both")
         q = 0 if q is None else bitstream.check_q(q, "encode_image: q")
         qm = self._check_qoffsets(qoffsets, None, 1, 1, "encode_image")
+        if rdoq is not None and np.ndim(rdoq) != 0:
+            raise ValueError("encode_image: rdoq is one weight for every tile of the file")
+        rdoq = self._check_rdoq(rdoq, 1, "encode_image")
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise ValueError("MCM.encode_image runs on the MI355X kernels: move the model to the GPU")
@@ -761,7 +809,8 @@ class MCM(CompressionModel):
             ids, zs, ys, lvs = [], [], [], []
             for t0 in range(0, g.T, tile_batch):
                 tiles, gray = ops.tile_cut_u8(x, img, g.O, t0, min(tile_batch, g.T - t0))
-                _, _, i, z, y, lv = self._encode_sections(tiles, image_scores(gray, img, patch), lanes, z_lanes, qv, qm)
+                _, _, i, z, y, lv = self._encode_sections(tiles, image_scores(gray, img, patch), lanes, z_lanes, qv, qm,
+                                                          None if rdoq is None else rdoq[0])
                 ids.append(i)
                 lvs.append(lv)
                 zs += list(z)
@@ -1265,6 +1314,17 @@ class _Executor:
             return q
         return torch.tensor(q, dtype=torch.int32).to(self.device)
 
+    def _rdo_dev(self, rdoq):
+        """the per-image weights of the rate-distortion optimised quantisation on the device (float32 [B], one upload)
+        with the counters of moved symbols (int32 [B]) and the tables the decision reads, or None for today's kernels"""
+        if rdoq is None:
+            return None
+        gc = self.m.gaussian_conditional
+        _, sizes, offsets = gc.device_tables(self.device)
+        return SimpleNamespace(w=torch.tensor(rdoq, dtype=torch.float32).to(self.device),
+                               rate=gc.device_rate_table(self.device), sizes=sizes, offsets=offsets,
+                               changed=torch.zeros(self.batch, dtype=torch.int32, device=self.device))
+
     # ------------------------------------------------------------------ per-patch quantiser steps (DESIGN.md §3.19)
     def _map_upload(self, qm):
         """MCM._check_qoffsets' pair with everything of it that lives on the host uploaded (before the first launch)
@@ -1314,7 +1374,7 @@ class _Executor:
             levels, status = ops.qlevels_select(shuf, K, len(offs), level_map=src)
         return dict(levels=levels, status=status if on_device else None, offsets=rows, who="qlevels")
 
-    def _analysis(self, imgs, scores, qd=None, qm=None):
+    def _analysis(self, imgs, scores, qd=None, qm=None, rdo=None):
         """the eval forward's analysis path with symbol / index outputs -> (zsym [B][N][hz*hz], y sym and idx
         [slice][image][channel][pixel], ids_restore), all on the device; qd: _q_dev's positions; qm: _map_upload's
         tuple, the levels' status then in self.last_levels_status"""
@@ -1322,7 +1382,7 @@ class _Executor:
         qmap = None
         if qm is not None:
             qmap, self.last_levels_status = self._encode_map(qm, scores, self.last_ids_shuffle, qd)
-        sym, idx = self._analysis_slices(qd, qmap)
+        sym, idx = self._analysis_slices(qd, qmap, rdo)
         return zsym, sym, idx, rest
 
     def _analysis_head(self, imgs, scores):
@@ -1339,14 +1399,17 @@ class _Executor:
         self._h_s()
         return zsym, rest
 
-    def _analysis_slices(self, qd=None, qmap=None):
+    def _analysis_slices(self, qd=None, qmap=None, rdo=None):
         """the slice loop of _analysis on what _analysis_head left (Y32, the h_s outputs) -> (sym, idx); it may be
-        run again at another qd or qmap (int32 [B, K], which takes precedence): nothing it reads is written by it"""
+        run again at another qd or qmap (int32 [B, K], which takes precedence): nothing it reads is written by it.
+        rdo: _rdo_dev's, whose counters of moved symbols are zeroed here and then hold this run's"""
         m, B = self.m, self.batch
         S, sw, HW = m.num_slices, self.sw, self.g * self.g
         sym = torch.empty(S * B * sw * HW, dtype=torch.int32, device=self.device)
         idx = torch.empty_like(sym)
-        self._slices(self._gc_compress(sym, idx, qd, qmap))
+        if rdo is not None:
+            rdo.changed.zero_()
+        self._slices(self._gc_compress(sym, idx, qd, qmap, rdo))
         return sym, idx
 
     def _code_z(self, zsym, z_lanes):
@@ -1368,21 +1431,25 @@ class _Executor:
             enc = self._dev_encoder = DeviceRansEncoder()
         return enc
 
-    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1, q=None, qm=None):
+    def compress_batch(self, imgs, scores, lanes=1, z_lanes=1, q=None, qm=None, rdoq=None):
         """compress with the device coder: the same symbol / index buffers, coded as one y and one z record per
         image (image b's y stream = its [slice][channel][pixel] symbols) of lanes / z_lanes lanes
         (coder.encode_record); one lane is the plain stream, the reference's batch-1 format B times.  q: None or B
         ladder positions, uploaded once before the first launch; qm: MCM._check_qoffsets' pair
-        (§3.19)"""
+        (§3.19); rdoq: None or B weights, uploaded with q (§3.21)"""
         hz = self.hz
         qd = self._q_dev(q)
+        rdo = self._rdo_dev(rdoq)
         if qm is not None:
             qm = self._map_upload(qm)
-        zsym, sym, idx, rest = self._analysis(imgs, scores, qd, qm)
+        zsym, sym, idx, rest = self._analysis(imgs, scores, qd, qm, rdo)
         z_strings = self._code_z(zsym, z_lanes)
         y_strings = self._code_y(sym, idx, lanes)
-        self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # rate diagnostics
+        self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx,  # rate diagnostics
+                                         **({} if rdo is None else {"y_changed": rdo.changed}))
         out = {"string": [y_strings, z_strings], "shape": torch.Size([hz, hz]), "ids_restore": rest}
+        if rdoq is not None:
+            out["rdoq"] = list(rdoq)
         if qm is not None:
             if self.last_levels_status is not None:
                 self._raise_levels(self.last_levels_status.cpu().numpy(), "compress_batch")
@@ -1391,17 +1458,19 @@ class _Executor:
             out["lanes"] = (lanes, z_lanes)
         return out
 
-    def compress_batch_target(self, imgs, scores, lanes, z_lanes, targets, fixed_bytes, qm=None):
+    def compress_batch_target(self, imgs, scores, lanes, z_lanes, targets, fixed_bytes, qm=None, rdoq=None):
         """compress_batch with per image the smallest q of the ladder at which fixed_bytes(q) + its z record + its y
         record is at most targets[b] -> (z records, y records, q per image).  Lower-bound bisection over Q_MIN..Q_MAX
         for all images at once (hi = Q_MAX + 1 stands for "no q fits" and is never probed): at most 7 probes, each the
         slice loop and the y coder at the images' current midpoints; the analysis head and the z records are done
         once.  An image's record is the one of its smallest successful probe; where none fits, of its last probe,
         which is q = Q_MAX.  The size is taken to be non-increasing in q.  qm (MCM._check_qoffsets' pair): q is the
-        base position, the levels are selected once and the map is rebuilt per probe (tmae_qmap_build)."""
+        base position, the levels are selected once and the map is rebuilt per probe (tmae_qmap_build).  rdoq: None
+        or B weights (§3.21), the same in every probe."""
         from .bitstream import Q_MAX, Q_MIN
 
         B = self.batch
+        rdo = self._rdo_dev(rdoq)
         if qm is not None:
             qm = self._map_upload(qm)
         zsym, rest = self._analysis_head(imgs, scores)
@@ -1413,7 +1482,8 @@ class _Executor:
         while any(l < h for l, h in zip(lo, hi)):
             mid = [(l + h) // 2 if l < h else min(l, Q_MAX) for l, h in zip(lo, hi)]  # settled images: any valid q
             qd = self._q_dev(mid)
-            sym, idx = self._analysis_slices(qd, None if qm is None else ops.qmap_build(self.last_levels, qd, qm[2]))
+            sym, idx = self._analysis_slices(qd, None if qm is None else ops.qmap_build(self.last_levels, qd, qm[2]),
+                                             rdo)
             y_strings = self._code_y(sym, idx, lanes)
             for b in range(B):
                 if lo[b] >= hi[b]:
@@ -1426,7 +1496,8 @@ class _Executor:
                         kept[b] = (Q_MAX, y_strings[b])
         if qm is not None and lstatus is not None:
             self._raise_levels(lstatus.cpu().numpy(), "encode_bytes")
-        self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx)  # of the last probe
+        self.last_streams = _LazyStreams(z_symbols=zsym, y_symbols=sym, y_indexes=idx,  # of the last probe
+                                         **({} if rdo is None else {"y_changed": rdo.changed}))
         return z_strings, [k[1] for k in kept], [k[0] for k in kept]
 
     def _z_indexes(self):
@@ -1638,9 +1709,10 @@ class _Executor:
                                     dt, M, self.YPRE, M, B, HW, nbs, sw, bound, qd)
         return step
 
-    def _gc_compress(self, sym, idx, qd=None, qmap=None):
+    def _gc_compress(self, sym, idx, qd=None, qmap=None, rdo=None):
         """eval step + int32 symbols / scale indexes in the coder's [slice][image][channel][pixel] order; qd: per-image
-        ladder positions on the device (the _q kernel, which skips the likelihoods nobody reads here) or None"""
+        ladder positions on the device (the _q kernel, which skips the likelihoods nobody reads here) or None; rdo:
+        _rdo_dev's (the _rdo kernel for all three cases of the step) or None"""
         gc = self.m.gaussian_conditional
         M, sw, B, HW, dt = self.m.latent_depth, self.sw, self.batch, self.g * self.g, self.dtype
         table = gc.scale_table
@@ -1648,7 +1720,11 @@ class _Executor:
         per = B * sw * HW
 
         def step(i0, nbs, mu, sigma, ms_stride):
-            if qmap is not None:
+            if rdo is not None:
+                ops.gc_slices_code_rdo(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, None, M, self.SUPY, dt, M,
+                                       self.YPRE, M, B, HW, nbs, sw, sym[i0 * per:], idx[i0 * per:], table, bound, qd,
+                                       qmap, rdo.w, rdo.rate, rdo.sizes, rdo.offsets, rdo.changed)
+            elif qmap is not None:
                 ops.gc_slices_code_qm(self.Y32, M, i0 * sw, mu, sigma, ms_stride, sw, None, M, self.SUPY, dt, M,
                                       self.YPRE, M, B, HW, nbs, sw, sym[i0 * per:], idx[i0 * per:], table, bound, qmap)
             elif qd is None:

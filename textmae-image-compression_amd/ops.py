@@ -20,7 +20,7 @@ __all__ = [
     "mask_rows", "decoder_pred", "conv3x3", "lic_stack", "pack_lic_stack_weight", "lic_stack_fits", "gc_slices", "eb_likelihood", "eb_aux_loss",
     "gc_likelihood", "nhwc_to_nchw", "bpp", "gemm_plan", "force_gemm_tile", "GEMM_TILES", "mha_plan", "mha_force_stream", "dtype_code", "gc_slices_code", "gc_indexes",
     "gc_dequantize", "gc_slices_fwd_q", "gc_slices_code_q", "gc_indexes_q", "gc_dequantize_q",
-    "gc_slices_fwd_qm", "gc_slices_code_qm", "gc_indexes_qm", "gc_dequantize_qm",
+    "gc_slices_fwd_qm", "gc_slices_code_qm", "gc_indexes_qm", "gc_dequantize_qm", "gc_slices_code_rdo",
     "qlevels_select", "qlevels_pack", "qlevels_unpack", "qmap_build",
     "gc_pmf", "eb_pmf", "eb_symbols", "eb_dequantize", "invert_permutation", "mae_masking",
     "rans_stream_cap_words", "rans_encode_streams", "rans_pack_streams", "rans_decode_streams",
@@ -554,6 +554,36 @@ def gc_slices_code_qm(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, lik, Mtot, yhat
     _lib.call("tmae_gc_slices_code_qm", _p(y), ldy, yoff, _p(mu), _p(sigma), ms_stride, ld_ms, _p(lik), Mtot, _p(yhat),
               dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, n, HW, nslices, sw, _p(symbols), _p(indexes),
               st.data_ptr(), st.numel(), float(scale_bound), _qmap_ptr(qmap, n, HW), _stream())
+
+
+def gc_slices_code_rdo(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, lik, Mtot, yhat, yhat_dtype, ld_yhat, yhat32, ld32,
+                       n, HW, nslices, sw, symbols, indexes, scale_table, scale_bound, q, qmap, rdo_w, rate_table,
+                       cdf_sizes, cdf_offsets, changed=None):
+    """gc_slices_code_q / _qm with rate-distortion optimised quantisation: q int32 [n] or None, qmap
+    int32 [n, HW] or None (takes precedence), both None = step 1; rdo_w float32 [n] on the device, the weights in
+    squared latent units per bit (0 = plain rounding, bit for bit); rate_table float32 [nscale, width], cdf_sizes /
+    cdf_offsets int32 [nscale]: GaussianConditional.device_rate_table() and the device_tables() it belongs to;
+    changed: int32 [n], zeroed by the caller, to which the elements whose symbol left the rounded one are added"""
+    st = _need(scale_table.contiguous(), torch.float32, "scale_table")
+    _need(rdo_w, torch.float32, "rdo_w")
+    if rdo_w.numel() != n:
+        raise ValueError(f"rdo_w holds {rdo_w.numel()} entries for {n} images")
+    _need(rate_table, torch.float32, "rate_table")
+    _need(cdf_sizes, torch.int32, "cdf_sizes")
+    _need(cdf_offsets, torch.int32, "cdf_offsets")
+    if rate_table.dim() != 2 or not rate_table.is_contiguous() or rate_table.shape[0] != st.numel() or \
+            cdf_sizes.numel() != st.numel() or cdf_offsets.numel() != st.numel():
+        raise ValueError(f"rate_table {tuple(rate_table.shape)}, {cdf_sizes.numel()} sizes and {cdf_offsets.numel()} "
+                         f"offsets for {st.numel()} scales: one contiguous row, size and offset per scale")
+    if changed is not None:
+        _need(changed, torch.int32, "changed")
+        if changed.numel() < n:
+            raise ValueError(f"changed holds {changed.numel()} entries for {n} images")
+    _lib.call("tmae_gc_slices_code_rdo", _p(y), ldy, yoff, _p(mu), _p(sigma), ms_stride, ld_ms, _p(lik), Mtot, _p(yhat),
+              dtype_code(yhat_dtype), ld_yhat, _p(yhat32), ld32, n, HW, nslices, sw, _p(symbols), _p(indexes),
+              st.data_ptr(), st.numel(), float(scale_bound), _q_ptr(q, n),
+              None if qmap is None else _qmap_ptr(qmap, n, HW), rdo_w.data_ptr(), rate_table.data_ptr(),
+              rate_table.shape[1], cdf_sizes.data_ptr(), cdf_offsets.data_ptr(), _p(changed), _stream())
 
 
 def gc_slices_fwd_qm(y, ldy, yoff, mu, sigma, ms_stride, ld_ms, noise, lik, Mtot, yhat, yhat_dtype, ld_yhat, yhat32,

@@ -114,12 +114,13 @@ def inference(model, x, ori_shape, total_score, file_name=None, output_dir=None,
 
 @torch.no_grad()
 def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_dir, output_dir=None, lanes=None,
-                        original_size=False, q=None, qoffsets=None):
+                        original_size=False, q=None, qoffsets=None, rdoq=None):
     """--bitstream DIR: encode_bytes -> DIR/<name>.tmc -> read the file back -> decode_bytes.  The bpp is that of
     the file, 8 * size / pixels: header and side information counted in full.  original_size takes the size the
     blob itself recorded.  q (--q N): the y quantiser step's ladder position (MCM.encode_bytes), read back from the
     file by decode_bytes.  qoffsets (--q-offsets): a step per kept patch, recorded in the file
-    too."""
+    too.  rdoq (--rdoq W): rate-distortion optimised quantisation of y at the encoder (§3.21); the file says nothing
+    of it and decodes as any other."""
     device = next(model.parameters()).device
     x = x.to(device)
     total_score = total_score.to(device)
@@ -127,7 +128,8 @@ def inference_bitstream(model, x, ori_shape, total_score, file_name, bitstream_d
     torch.cuda.synchronize()
     start = time.time()
     blobs = model.encode_bytes(x, total_score, lanes=1 if lanes is None else lanes,
-                               orig_sizes=[(int(ori_shape[0]), int(ori_shape[1]))], q=q, qoffsets=qoffsets)
+                               orig_sizes=[(int(ori_shape[0]), int(ori_shape[1]))], q=q, qoffsets=qoffsets,
+                               rdoq=rdoq)
     enc_time = time.time() - start
     with open(path, "wb") as f:
         f.write(blobs[0])
@@ -150,7 +152,7 @@ MS_SSIM_MIN_SIDE = 161  # five scales of an 11-tap window: the smaller side must
 
 @torch.no_grad()
 def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, output_dir=None, lanes=None, tile_batch=16,
-                    q=None, qoffsets=None):
+                    q=None, qoffsets=None, rdoq=None):
     """--tiled: the image at its own resolution, rgb uint8 [H, W, 3] -> MCM.encode_image -> (with bitstream_dir)
     DIR/<name>.tmt, read back -> MCM.decode_image.  PSNR / MS-SSIM against the original pixels at that resolution,
     bpp = 8 * file size / (W * H).  An image too small for MS-SSIM's five scales gets PSNR only (no "ms-ssim")."""
@@ -162,7 +164,7 @@ def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, outpu
     torch.cuda.synchronize()
     start = time.time()
     blob = model.encode_image(x, overlap=overlap, lanes=1 if lanes is None else lanes, tile_batch=tile_batch, q=q,
-                              qoffsets=qoffsets)
+                              qoffsets=qoffsets, rdoq=rdoq)
     enc_time = time.time() - start
     if bitstream_dir is not None:
         path = os.path.join(bitstream_dir, Path(file_name).stem + ".tmt")
@@ -191,7 +193,7 @@ def inference_tiled(model, rgb, file_name, overlap=32, bitstream_dir=None, outpu
 
 
 def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_dir=None, tile_batch=16, q=None,
-               qoffsets=None):
+               qoffsets=None, rdoq=None):
     """--tiled counterpart of eval_model over image files: every metric averaged over the images that have it
     -> (metrics, number of images with MS-SSIM)"""
     from PIL import Image
@@ -202,7 +204,7 @@ def eval_tiled(model, output_dir, filepaths, overlap=32, lanes=None, bitstream_d
     sums, counts = defaultdict(float), defaultdict(int)
     for p in filepaths:
         rv = inference_tiled(model, np.array(Image.open(p).convert("RGB")), p.name, overlap, bitstream_dir, output_dir,
-                             lanes, tile_batch, q, qoffsets)
+                             lanes, tile_batch, q, qoffsets, rdoq)
         for k, v in rv.items():
             sums[k] += v
             counts[k] += 1
@@ -249,7 +251,7 @@ def load_test_images(paths, size=224, device=None):
 
 
 def eval_model(model, output_dir, images, scores, names=None, entropy_estimation=False, lanes=None,
-               original_size=False, bitstream_dir=None, q=None, qoffsets=None):
+               original_size=False, bitstream_dir=None, q=None, qoffsets=None, rdoq=None):
     """testing.py:128-165 over pre-loaded (img [1,3,S,S], orig_shape) pairs and a [N, L] score tensor; with
     bitstream_dir every image goes through its .tmc file there (inference_bitstream; needs names)"""
     metrics = defaultdict(float)
@@ -265,7 +267,7 @@ def eval_model(model, output_dir, images, scores, names=None, entropy_estimation
             rv = inference_entropy_estimation(model, img, ts, q=q, qoffsets=qoffsets)
         elif bitstream_dir is not None:
             rv = inference_bitstream(model, img, ori_shape, ts, names[i], bitstream_dir, output_dir, lanes=lanes,
-                                     original_size=original_size, q=q, qoffsets=qoffsets)
+                                     original_size=original_size, q=q, qoffsets=qoffsets, rdoq=rdoq)
         else:
             rv = inference(model, img, ori_shape, ts, None if names is None else names[i], output_dir, lanes=lanes,
                            original_size=original_size)
@@ -322,7 +324,23 @@ def setup_args():
                    help="a quantiser step per kept patch (DESIGN.md §3.19): 2..16 ladder offsets in -64..64, the first "
                         "for the most text-like share of the kept patches, added to --q (default 0); with "
                         "--bitstream / --tiled / --entropy-estimation")
+    p.add_argument("--rdoq", type=_rdoq, default=None, metavar="W",
+                   help="rate-distortion optimised quantisation of y at the encoder (DESIGN.md §3.21): a y symbol moves "
+                        "one step toward zero where W times the bits that saves exceeds the squared latent error it "
+                        "adds; W >= 0 in squared latent units per bit, 0 = plain rounding; with --bitstream / --tiled")
     return p
+
+
+def _rdoq(text):
+    import math
+
+    try:
+        w = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--rdoq {text!r} is not a number") from None
+    if not (math.isfinite(w) and w >= 0):
+        raise argparse.ArgumentTypeError(f"--rdoq {text} must be finite and >= 0")
+    return w
 
 
 def _q_offsets(text):
@@ -353,6 +371,10 @@ def main(argv):
         print("Error: --q-offsets needs --bitstream DIR or --tiled (real files) or --entropy-estimation (the "
               "estimate).", file=sys.stderr)
         sys.exit(1)
+    if args.rdoq is not None and not (args.tiled or args.bitstream is not None) or \
+            args.rdoq is not None and args.entropy_estimation:
+        print("Error: --rdoq is an encoder decision: it needs --bitstream DIR or --tiled (real files).", file=sys.stderr)
+        sys.exit(1)
     if not args.tiled:
         ds = Path(args.dataset)
         score_file = ds.parent / f"{ds.name}_scores" / "test.pt"
@@ -372,11 +394,12 @@ def main(argv):
         model.update(force=True)
         if args.tiled:
             m, with_msssim = eval_tiled(model, args.output_path, filepaths, args.overlap, lanes=args.lanes,
-                                        bitstream_dir=args.bitstream, q=args.q, qoffsets=args.q_offsets)
+                                        bitstream_dir=args.bitstream, q=args.q, qoffsets=args.q_offsets,
+                                        rdoq=args.rdoq)
         else:
             m = eval_model(model, args.output_path, images, scores, [p.name for p in filepaths],
                            args.entropy_estimation, lanes=args.lanes, original_size=args.original_size,
-                           bitstream_dir=args.bitstream, q=args.q, qoffsets=args.q_offsets)
+                           bitstream_dir=args.bitstream, q=args.q, qoffsets=args.q_offsets, rdoq=args.rdoq)
         for k, v in m.items():
             results[k].append(v)
     desc = "entropy estimation" if args.entropy_estimation else args.entropy_coder
@@ -390,6 +413,8 @@ def main(argv):
         desc += f"; y quantiser step 2^({args.q}/8)"
     if args.q_offsets is not None:
         desc += f"; per-patch ladder offsets {','.join(str(v) for v in args.q_offsets)} by score rank"
+    if args.rdoq is not None:
+        desc += f"; rate-distortion optimised quantisation of y, weight {args.rdoq:g} per bit (encoder only)"
     output = {"name": "MCM", "description": f"Inference ({desc})", "results": results}
     print(json.dumps(output, indent=2))
     os.makedirs(args.output_path, exist_ok=True)

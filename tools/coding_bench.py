@@ -10,9 +10,13 @@ batch, and the bytes per image of both formats.  --lanes 1,4,16,64 adds one devi
 --bitstream adds, beside every device column, a "bytes" column: MCM.encode_bytes + decode_bytes at the same lanes (the
 self-contained blobs: compress_batch's records behind a header and the packed kept ids), the mean blob size split
 into header, ids, z and y, and whether either call is slower than its device column by more than the spread.
+--rdoq W adds, beside every device column, an "_rdoq" column: compress_batch(rdoq=W) (rate-distortion optimised
+quantisation of y; the decoder is the same call), alternating with the others; it reports the cost
+against its device column by the same rule, the symbols moved per image and the bytes.  Those columns reconstruct
+other images than the plain ones, on purpose, and are left out of the equality check.
 
     python tools/coding_bench.py [--rounds 10] [--warmup 3] [--batches 64,1] [--lanes 1,4,16,64] [--bitstream]
-                                 [--out profiles/coding_device/x.json]
+                                 [--rdoq W] [--out profiles/coding_device/x.json]
 """
 import argparse
 import json
@@ -62,7 +66,7 @@ def blob_split(blobs):
             "total": round(sum(len(b) for b in blobs) / n, 1)}
 
 
-def run_batch(model, batch, img, rounds, warmup, dev, lanes=(), bitstream=False):
+def run_batch(model, batch, img, rounds, warmup, dev, lanes=(), bitstream=False, rdoq=None):
     L = model.encoder_embed.num_patches
     x, s = inputs(batch, img, L, 1000, dev)
     paths = {
@@ -76,6 +80,15 @@ def run_batch(model, batch, img, rounds, warmup, dev, lanes=(), bitstream=False)
             paths[f"device_l{n}"] = (lambda n=n: model.compress_batch(x, s, lanes=n),
                                      lambda c, n=n: model.decompress_batch(c["string"], c["shape"], c["ids_restore"],
                                                                            lanes=n))
+    rdo = {}  # rdoq column -> the device column it runs beside
+    if rdoq is not None:
+        for n in [1] + [n for n in lanes if n != 1]:
+            devname = "device" if n == 1 else f"device_l{n}"
+            paths[devname + "_rdoq"] = (lambda n=n: model.compress_batch(x, s, lanes=n, rdoq=rdoq),
+                                        lambda c, n=n: model.decompress_batch(c["string"], c["shape"],
+                                                                              c["ids_restore"], lanes=n))
+            rdo[devname + "_rdoq"] = devname
+    changed = {}
     pairs = {}  # bytes column -> the device column it wraps
     if bitstream:
         for n in [1] + [n for n in lanes if n != 1]:
@@ -93,11 +106,13 @@ def run_batch(model, batch, img, rounds, warmup, dev, lanes=(), bitstream=False)
                     t[f"{p}_compress"].append(tc)
                     t[f"{p}_decompress"].append(td)
                 rec[p] = d["x_hat"]
+                if p in rdo:
+                    changed[p] = float(model._exec.last_streams["y_changed"].mean())
                 if p in pairs:
                     size[p], split[p] = sum(len(b) for b in c) / batch, blob_split(c)
                 else:
                     size[p] = sum(len(b) for part in c["string"] for b in part) / batch
-    if not all(torch.equal(rec["host"], rec[p]) for p in paths):
+    if not all(torch.equal(rec["host"], rec[p]) for p in paths if p not in rdo):
         raise SystemExit("coding_bench: the paths reconstruct different images")
     out = {k: stats(v) for k, v in t.items()}
     for p in paths:
@@ -113,6 +128,12 @@ def run_batch(model, batch, img, rounds, warmup, dev, lanes=(), bitstream=False)
             v = out[f"{p}_total"]
             out[f"{p}_faster_than_host_beyond_spread"] = bool(v["max_ms"] < h["min_ms"])
             out[f"{p}_faster_than_device_beyond_spread"] = bool(v["max_ms"] < d["min_ms"])
+    for p, q in rdo.items():  # what the decision costs, by the rule of the bytes columns
+        for k in ("compress", "decompress", "total"):
+            a, b = out[f"{p}_{k}"], out[f"{q}_{k}"]
+            out[f"{p}_{k}_vs_{q}"] = {"median_delta_ms": round(a["median_ms"] - b["median_ms"], 3),
+                                      "slower_beyond_spread": bool(a["min_ms"] > b["max_ms"])}
+        out[f"{p}_y_changed_per_image"] = round(changed[p], 1)
     if pairs:
         out["blob_bytes_per_image"] = split
     for p, q in pairs.items():  # slower beyond the spread: the fastest blob round is slower than the slowest device one
@@ -134,6 +155,8 @@ def main():
     ap.add_argument("--lanes", default="", help="comma-separated y lane counts (powers of two up to 64)")
     ap.add_argument("--bitstream", action="store_true",
                     help="add encode_bytes / decode_bytes beside every device column")
+    ap.add_argument("--rdoq", type=float, default=None, metavar="W",
+                    help="add compress_batch(rdoq=W) beside every device column")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if args.rounds < 2:
@@ -153,8 +176,11 @@ def main():
            "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "warmup": args.warmup}
     if lanes:
         res["lanes"] = lanes
+    if args.rdoq is not None:
+        res["rdoq"] = args.rdoq
     for b in (int(v) for v in args.batches.split(",")):
-        res[f"batch_{b}"] = run_batch(model, b, args.img, args.rounds, args.warmup, dev, lanes, args.bitstream)
+        res[f"batch_{b}"] = run_batch(model, b, args.img, args.rounds, args.warmup, dev, lanes, args.bitstream,
+                                      args.rdoq)
     line = json.dumps(res)
     print(line)
     if args.out:

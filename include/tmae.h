@@ -671,6 +671,10 @@ typedef struct tmae_wgrad_args {
 int tmae_wgrad(const tmae_wgrad_args* args, int dtype, void* stream);
 long long tmae_wgrad_workspace(int M, int N, int K, int dtype);
 long long tmae_wgrad_workspace_nb(int M, int N, int K, int dtype, int slot_div, int nb);
+/* diagnostics: the kernel tmae_wgrad launches for this problem as "tn<bf16,256x256,8w,s2,kc320>" (operand type,
+ * tile, waves, K splits, K rows per split).  K <= 0 plans as K = 1 (tmae_wgrad itself rejects it); the f32 path
+ * runs nb problems one launch each, so its plan does not depend on nb. */
+int tmae_wgrad_plan(int M, int N, int K, int dtype, int slot_div, int nb, char* out, int len);
 
 /* data gradient of y = x w^T: dx[M][K] = dy[M][N] wt[K][N]^T (wt = w transposed, dtype); dy rows remapped
  * like tmae_linear_fwd.  out (dtype, or f32 with out_f32) = dx * gelu'(pre) when pre is given (the GELU

@@ -222,6 +222,7 @@ SIGNATURES = {
     "tmae_mha_bwd": [P, P, P, P, P, I, I, I, I, F, I, P],
     "tmae_patch_gather": [P, P, P, I, I, I, I, I, I, I, I, P],
     "tmae_wgrad": [ctypes.POINTER(WgradArgs), I, P],
+    "tmae_wgrad_plan": [I, I, I, I, I, I, ctypes.c_char_p, I],
     "tmae_dgrad_linear": [P, I, I, I, I, P, I, I, I, P, I, I, P, I, P, I, I, P],
     "tmae_conv_dgrad": [ctypes.POINTER(ConvDgradArgs), I, P],
     "tmae_relayout": [P, P, I, I, I, I, I, LL, LL, LL, LL, P],

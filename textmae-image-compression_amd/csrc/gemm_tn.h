@@ -388,8 +388,12 @@ gemm_tn_f32_kernel(AS as, BS bs, EpiSplitWs epi, int M, int N, int K, int kchunk
 // ------------------------------------------------------------------ launch
 struct TnPlan { int bn, bm, nw, splits, kchunk; };
 
+// K <= 0 plans as K = 1 and an empty output as one tile (one split of one K-step): the workspace queries and the
+// plan string stay defined for them (kchunk = 0 and tiles = 0 were integer divisions by zero); tmae_wgrad itself
+// rejects K <= 0 and returns early for an empty output.
 static inline TnPlan tn_plan(int M, int N, int K, bool bf, int slot_div = 1, int nb = 1) {
   TnPlan p;
+  K = std::max(K, 1);
   if (!bf) {
     p.bn = 64; p.bm = 64; p.nw = 4;
   } else {
@@ -398,7 +402,7 @@ static inline TnPlan tn_plan(int M, int N, int K, bool bf, int slot_div = 1, int
     if (u256 > 0.7 && t256 * 8 >= 64) { p.bn = 256; p.bm = 256; p.nw = 8; }
     else { p.bn = 128; p.bm = 128; p.nw = 4; }
   }
-  const int tiles = ceil_div(N, p.bn) * ceil_div(M, p.bm) * std::max(1, nb);  // nb problems share the slots
+  const int tiles = std::max(1, ceil_div(N, p.bn) * ceil_div(M, p.bm) * std::max(1, nb));  // nb problems share the slots
   const int slots = (p.nw == 8 ? 256 : 512) / std::max(1, slot_div);
   const int kmin = bf ? 256 : 128;
   // splits: as many as fit ONE round of the slots (floor): with the ceiling, tiles * splits overshot the

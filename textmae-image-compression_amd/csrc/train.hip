@@ -185,8 +185,19 @@ static int tmae_wgrad_reduce(const float* ws, int splits, int M, int N, float* o
 extern "C" int tmae_wgrad(const tmae_wgrad_args* a, int dtype, void* stream) {
   TMAE_REQUIRE(a != nullptr && a->a && a->b && a->work && a->out, "tmae_wgrad: null argument");
   if (a->M == 0 || a->N == 0) return TMAE_OK;
+  TMAE_REQUIRE(a->K > 0, "tmae_wgrad: K=%d: an empty reduction is not supported (zero the gradient instead)", a->K);
   if (dtype == TMAE_BF16) return wgrad_t<bf16>(*a, (hipStream_t)stream);
   return wgrad_t<float>(*a, (hipStream_t)stream);
+}
+
+// diagnostics: what wgrad_t launches for this problem, from the same tn_plan call
+extern "C" int tmae_wgrad_plan(int M, int N, int K, int dtype, int slot_div, int nb, char* out, int len) {
+  TMAE_REQUIRE(out != nullptr && len > 0 && M >= 0 && N >= 0, "tmae_wgrad_plan: bad arguments");
+  const bool bf = dtype == TMAE_BF16;
+  // the f32 parity path runs a batched launch as one launch per problem, each planned alone (wgrad_t)
+  const TnPlan p = tn_plan(M, N, K, bf, slot_div, (bf && nb > 1) ? nb : 1);
+  snprintf(out, len, "tn<%s,%dx%d,%dw,s%d,kc%d>", bf ? "bf16" : "f32", p.bn, p.bm, p.nw, p.splits, p.kchunk);
+  return TMAE_OK;
 }
 
 extern "C" long long tmae_wgrad_workspace(int M, int N, int K, int dtype) {

@@ -126,6 +126,14 @@ def wgrad(a, b, M, N, K, out, dtype, lda=None, ldb=None, a_remap=(None, 0, 0), b
     return out
 
 
+def wgrad_plan(M: int, N: int, K: int, dtype, slot_div: int = 1, nb: int = 1) -> str:
+    """the kernel wgrad launches for this problem, e.g. 'tn<bf16,256x256,8w,s2,kc320>' (tile, waves, K splits, K rows
+    per split), from the same plan as the launch"""
+    buf = ctypes.create_string_buffer(96)
+    _lib.call("tmae_wgrad_plan", M, N, K, dtype_code(dtype), int(slot_div), int(nb), buf, len(buf))
+    return buf.value.decode()
+
+
 def dgrad_linear(dy, wt, M, N, K, dtype, out=None, pre=None, acc32=None, ldy=None, row_group=None, group_stride=0,
                  row_offset=0, ldo=None):
     """dx[M][K] = dy[M][N] W (wt = W^T [K][N] in dtype); out (dtype or f32) = dx * gelu'(pre); acc32 += dx"""
